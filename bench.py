@@ -14,7 +14,13 @@ Default workload = BASELINE config 3 (the north-star shape): 4-agent 32x32 grid,
 per GPU, FeAR on with weight -5 (configs/custom_fear_5.yaml).  value = all ranks' envs x N
 agents x steps / max-over-ranks wall time.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config c3|c2|c2env|c4|c1|c5|...] [--no-cpu-baseline]
+  python bench.py [--gpus N --steps K --warmup W] [--config c3|c2|c2env|c4|c1|c5|...] [--dump-outputs DIR]
+                   [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step,
+the config and the untimed bookkeeping of the timed steps).  --full adds what takes runs of its
+own: the profiled steps behind the per-kernel / roofline figures, the FeAR sims count and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -274,6 +280,63 @@ def busy_ms(spans, kind: int):
     return total, len(iv)
 
 
+DUMP_BUDGET = 60 << 20  # bytes of .npy payload per --dump-outputs directory (below 64 MB with headers)
+
+
+def last_step_outputs(env, last_r, ro, gather, graph_n: int) -> dict:
+    """name -> device tensor of what the last timed step handed to its caller: the StepResult of
+    ``VecGridEnv.step`` / ``Rollout.step`` and, for a rollout, the actor's actions and
+    probabilities.  last_r: that StepResult when the step was issued eagerly; None when it ran
+    inside a graph replay, whose last captured call wrote the same buffers (the env's own, the
+    gather's last window slot, the replay ring's current slots)."""
+    if last_r is not None:
+        out = {n: getattr(last_r, n) for n in last_r.__dataclass_fields__}
+    else:
+        out = dict(env.out)
+        if gather is not None:  # one rank (graphs are captured on one rank only)
+            rets, done = gather._views(gather._recv[graph_n - 1, 0])
+            out["ep_return"] = rets[: gather.count]
+            out["done_copy" if ro is not None else "done"] = done[: gather.count]
+    if ro is not None and ro.replay is not None:
+        rp = ro.replay
+        cur, nxt = (ro.t - 1) % rp.S, ro.t % rp.S
+        if last_r is None:
+            out.update(shaped=rp.reward[cur], term=rp.term[cur], done=rp.done[cur])
+        if last_r is None or ro.patch:  # the local-window rollouts' obs are the ring's windows
+            out.update(obs=rp.obs[nxt], final_obs=rp.final_obs[cur])
+        out.update(actor_actions=ro._actions, actor_probs=rp.probs[cur])
+    return {n: t for n, t in out.items() if t is not None}
+
+
+def dump_outputs(path: str, tensors: dict, E: int, budget: int = DUMP_BUDGET) -> dict:
+    """Write each tensor as path/<name>.npy: float64 for float64 and for integers of 32 bits or
+    more (exact), float32 for everything else.  The arrays share ``budget`` bytes, the smallest
+    first: one that does not fit its share is cut down to a fixed, seeded sample of its envs (the
+    axis of length E), whose indices go to path/<name>_envs.npy.  -> name -> written shape."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    wide = (torch.float64, torch.int32, torch.int64)
+    size = {n: t.numel() * (8 if t.dtype in wide else 4) for n, t in tensors.items()}
+    written, left = {}, budget
+    for i, n in enumerate(sorted(tensors, key=lambda n: (size[n], n))):
+        t = tensors[n]
+        share = left // (len(tensors) - i)
+        if size[n] > share and E in t.shape:
+            axis = list(t.shape).index(E)
+            keep = max(1, int(share // (size[n] // E + 8)))  # + 8: the env's index in <name>_envs.npy
+            envs = np.sort(np.random.default_rng(0).choice(E, keep, replace=False))
+            t = t.index_select(axis, torch.as_tensor(envs, device=t.device))
+            a = envs.astype(np.float64)
+            np.save(os.path.join(path, n + "_envs.npy"), a)
+            left -= a.nbytes
+        a = t.to(torch.float64 if t.dtype in wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, n + ".npy"), a)
+        left -= a.nbytes
+        written[n] = list(a.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -282,7 +345,14 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--envs", type=int, default=0, help="override envs per GPU")
     ap.add_argument("--fear", type=int, default=-1, help="override FeAR on (1) / off (0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the profiled steps (per-kernel and "
+                         "roofline figures, FeAR sims) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: large arrays as a fixed sample of their envs; "
+                         "rank r > 0 writes DIR/rank<r>/)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--updates-per-step", type=int, default=0,
                     help="c5 only: MADDPG updates (batch 128, one HIP-graph replay each) per env step")
     ap.add_argument("--dense-learn", action="store_true",
@@ -295,10 +365,10 @@ def main():
                     help="with --updates-per-step: replay the update as a HIP graph instead (A/B)")
     ap.add_argument("--eager-learn", action="store_true",
                     help="with --updates-per-step: issue the update eagerly instead of replaying its HIP graph (A/B)")
-    ap.add_argument("--profile-steps", type=int, default=64,
-                    help="after the timed region, time this many more steps' kernels with HIP events "
-                         "carried by their launches (the live roofline; 0 = none)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="with --full: after the timed region, time this many more steps' kernels with HIP "
+                         "events carried by their launches (the live roofline; default 64, 0 = none)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: the CPU baseline's sample")
     ap.add_argument("--cnn-torch", action="store_true",
                     help="c4cnn: the PyTorch CNN forward on the dense obs instead of gw_cnn_act (A/B)")
     ap.add_argument("--patch-torch", action="store_true",
@@ -330,6 +400,12 @@ def main():
                          "launches, -1 = auto: 16 for the launch-bound env-only workloads that run "
                          "synchronous obs on one rank, i.e. C1/C2, else eager)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.profile_steps is None:
+        args.profile_steps = 64 if args.full else 0
+    elif args.profile_steps > 0 and not args.full:
+        ap.error("--profile-steps: the profiled steps are part of --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start one rank per GPU ourselves, before any GPU call in this process
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -441,6 +517,7 @@ def main():
             gather.push()
         return r
 
+    ro = None
     if cfg.get("rollout"):  # c5: actor -> env -> replay (+ optional MADDPG updates) per step
         from marlnav.maddpg import MADDPG
         from marlnav.rollout import Rollout
@@ -548,13 +625,14 @@ def main():
     for i in range(0, n_graph, max(graph_n, 1)):
         graph.replay()
     t_first = []  # host time of the first eager timed steps (the pipeline fill is host-visible)
+    last_r = None  # what the last timed step returned (None: it ran inside a graph replay)
     for i in range(n_graph, args.steps):
         if len(t_first) < 4:
             th = time.perf_counter()
-            one_step(i)
+            last_r = one_step(i)
             t_first.append((time.perf_counter() - th) * 1e6)
         else:
-            one_step(i)
+            last_r = one_step(i)
     t_enq = time.perf_counter() - t0  # host time to enqueue the timed steps (host-bound if ~ wall)
     if cfg.get("rollout"):
         ro._flush()  # an unjoined FeAR step's statistics and return push (fear_async)
@@ -573,6 +651,10 @@ def main():
     wall = time.perf_counter() - t0
     gc.enable()
     gpu_ms = ev0.elapsed_time(ev1)
+    dumped = None
+    if args.dump_outputs:  # before anything else steps the env: the last timed step's buffers, fenced above
+        dumped = dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                              last_step_outputs(env, last_r, ro, gather, graph_n), E)
     spans = None
     sims = None
     if n_prof:
@@ -608,7 +690,43 @@ def main():
                     "cap": getattr(gather, "cap", None),
                     "mean_return_last_100": float(gather.completed(last=100).mean()) if int(gather.n_completed) else None}
 
-    if rank == 0:
+    line = None
+    if rank == 0:  # the headline line: the timed steps and their untimed bookkeeping
+        line = {
+            "metric": METRIC,
+            "value": world * E * N * args.steps / t_max,
+            "unit": "agent-env-steps/s",
+            "n_gpus": world,
+            # the process group the timed steps ran in (the driver's multi-GPU runs: RCCL over xGMI)
+            "process_group": {"size": world, "backend": dist.get_backend() if world > 1 else None,
+                              "packed_bytes_per_rank_per_step": gather.slot_bytes if (gather is not None and world > 1)
+                              else None},
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": t_max * 1e3 / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int32",
+            "data": "synthetic (device Philox spawns / scripted policy / random RL policy)",
+            "config": {"workload": cfg["workload"], "scenario": cfg["scenario"], "envs_per_gpu": E,
+                       "global_envs": world * E, "agents": N, "rl_agents": K, "grid": [env.H, env.W],
+                       "fear": cfg["fear"], "parallelism": f"env-sharded dp{world}", "obs_dtype": args.obs_dtype},
+            "full": args.full,
+            "kernels_ms": {"kernel_path": env.kernel_path,
+                           "stream_ms_per_step": gpu_ms / args.steps,
+                           "obs_async": obs_mode, "fear_async": env.fear_async,
+                           "graph_steps": graph_n, "obs_ring": n_ring,
+                           "host_enqueue_ms_per_step": t_enq * 1e3 / args.steps,
+                           "host_first_steps_us": [round(x, 1) for x in t_first]},
+            "last_step_episodes": {"completed": stats[1], "mean_return": stats[0] / max(stats[1], 1.0),
+                                   "mean_len": stats[6] / max(stats[1], 1.0)},
+            # completed-episode returns all-gathered every step (warmup + timed steps, all ranks)
+            "return_gather": gathered,
+            # --dump-outputs: the arrays written (name -> shape; rank 0's)
+            "dumped_outputs": dumped,
+        }
+    if rank == 0 and args.full:  # the profiled steps' per-kernel / roofline figures, the CPU baseline
         step_b, obs_b = algorithmic_bytes(N, K, cfg["patch"] ** 2 if cfg.get("patch") else HW,
                                           2 if args.obs_dtype == "bf16" else 4)
         avg_step_ms, avg_obs_ms = ms_step / max(nprof, 1), ms_obs / max(nprof, 1)
@@ -715,27 +833,10 @@ def main():
                         (1e12 if mfma else 1e9) / peak_u
         except (OSError, KeyError, ValueError, TypeError):
             pass
-        total_units = world * E * N * args.steps
-        line = {
-            "metric": METRIC,
-            "value": total_units / t_max,
-            "unit": "agent-env-steps/s",
-            "n_gpus": world,
-            # the process group the timed steps ran in (the driver's multi-GPU runs: RCCL over xGMI)
-            "process_group": {"size": world, "backend": dist.get_backend() if world > 1 else None,
-                              "packed_bytes_per_rank_per_step": gather.slot_bytes if (gather is not None and world > 1)
-                              else None},
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": t_max * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic (device Philox spawns / scripted policy / random RL policy)",
-            "config": {"workload": cfg["workload"], "scenario": cfg["scenario"], "envs_per_gpu": E,
-                       "global_envs": world * E, "agents": N, "rl_agents": K, "grid": [env.H, env.W],
-                       "fear": cfg["fear"], "parallelism": f"env-sharded dp{world}", "obs_dtype": args.obs_dtype},
+        line["kernels_ms"].update({"profiled_steps": nprof, "step_kernel": avg_step_ms, "obs_kernel": avg_obs_ms,
+                                   "fear_kernel": avg_fear_ms,
+                                   "spans_from": f"{n_prof} eager steps after the timed region"})
+        line.update({
             "roofline": {"bound": dom_bound, "kernel": dom, "achieved": achieved, "peak": peak_u,
                          "unit": "TFLOP/s" if mfma else "GB/s", "frac": achieved / peak_u if achieved else None,
                          "traffic": traffic, "traffic_source": traffic_src, "frac_rocprof": prof_frac,
@@ -771,18 +872,6 @@ def main():
                                              peak_u) if bytes_per_launch else None,
                          # every profiled kernel kind: busy time per step and its own roofline
                          "kernels": per_kind},
-            "kernels_ms": {"profiled_steps": nprof, "step_kernel": avg_step_ms, "obs_kernel": avg_obs_ms, "fear_kernel": avg_fear_ms,
-                           "kernel_path": env.kernel_path,
-                           "stream_ms_per_step": gpu_ms / args.steps,
-                           "obs_async": obs_mode, "fear_async": env.fear_async,
-                           "graph_steps": graph_n, "obs_ring": n_ring,
-                           "host_enqueue_ms_per_step": t_enq * 1e3 / args.steps,
-                           "host_first_steps_us": [round(x, 1) for x in t_first],
-                           "spans_from": f"{n_prof} eager steps after the timed region"},
-            "last_step_episodes": {"completed": stats[1], "mean_return": stats[0] / max(stats[1], 1.0),
-                         "mean_len": stats[6] / max(stats[1], 1.0)},
-            # completed-episode returns all-gathered every step (warmup + timed steps, all ranks)
-            "return_gather": gathered,
             # FeAR's integer work: the counterfactual world updates the FeAR kernels ran
             # per step (gw_count_sims over the profiled steps, after the exact de-duplication of
             # DESIGN §5.2) and the reference's nominal K (N - 1) 18 per env-step, per second at the
@@ -793,7 +882,7 @@ def main():
                 "ref_equiv_per_s": world * E * K * (N - 1) * 18 / (t_max / args.steps),
                 "dedup_factor": E * K * (N - 1) * 18 / sims if sims else None,
                 "unit": "world updates (custom/Responsibility.py:16-54 UpdateGWorld counterfactuals)"},
-        }
+        })
         rf = line["roofline"]
         if dom == "act_kernel":
             rf["precision"] = ACT_PRECISION
@@ -807,6 +896,7 @@ def main():
                       achieved_per_period=None, frac_per_period=None)
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     env.close()
     if world > 1:

@@ -32,6 +32,47 @@ def test_cli_help_without_gpu():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 0 and "--steps" in r.stdout and "--obs-dtype" in r.stdout
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_formats_and_budget(tmp_path):
+    """--dump-outputs: float64 stays float64, integers of 32 bits or more become float64 (exact),
+    everything else float32; None entries are the caller's to drop; an array above its share of
+    the budget is cut to the same seeded sample of its envs on every call, indices beside it."""
+    import numpy as np
+    import torch
+    E, K = 4096, 2
+    g = torch.Generator().manual_seed(3)
+    obs = torch.randint(-2, 3, (K, E, 8, 8), generator=g).to(torch.bfloat16)
+    tensors = {"obs": obs,
+               "reward": torch.randn(E, K, generator=g, dtype=torch.float64),
+               "done": torch.randint(0, 2, (E,), generator=g).to(torch.uint8),
+               "mask": torch.randint(0, 512, (E, K), generator=g).to(torch.int16),
+               "desc_copy": torch.randint(-2 ** 31, 2 ** 31 - 1, (E, 12), generator=g).to(torch.int32)}
+    budget = 1 << 20  # obs alone is 2 MB as float32: it is the only array sampled
+    shapes = bench.dump_outputs(str(tmp_path / "a"), tensors, E, budget=budget)
+    again = bench.dump_outputs(str(tmp_path / "b"), tensors, E, budget=budget)
+    assert shapes == again
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted([n + ".npy" for n in tensors] + ["obs_envs.npy"])
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(a.nbytes for a in got.values()) <= budget
+    for f in files:
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))
+    assert {n: a.dtype.name for n, a in got.items()} == {
+        "obs": "float32", "obs_envs": "float64", "reward": "float64", "done": "float32", "mask": "float32",
+        "desc_copy": "float64"}
+    for n in ("reward", "done", "mask", "desc_copy"):  # whole and exact
+        assert np.array_equal(got[n], tensors[n].numpy().astype(got[n].dtype)), n
+    envs = got["obs_envs"].astype(np.int64)
+    assert 0 < len(envs) < E and np.all(np.diff(envs) > 0) and shapes["obs"] == [K, len(envs), 8, 8]
+    assert np.array_equal(got["obs"], obs.float().numpy()[:, envs])
+
+
+def test_profiled_steps_need_full():
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--profile-steps", "8"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr
 
 
 def test_launch_plan_one_rank_per_gpu():

@@ -13,7 +13,7 @@ run() {  # name path cmd...
 for i in 1 2 3; do
   for nv in $LIBS; do
     n=${nv%%=*}; p=${nv#*=}
-    run $n "$p" timeout -k 10 200 python bench.py --config $CFG --no-cpu-baseline "$@" > $O/${n}_$i.log 2>&1 && python tools/bench_line.py $O/${n}_$i.log ${n}_$i || exit 1
+    run $n "$p" timeout -k 10 200 python bench.py --full --config $CFG --no-cpu-baseline "$@" > $O/${n}_$i.log 2>&1 && python tools/bench_line.py $O/${n}_$i.log ${n}_$i || exit 1
   done
 done
 [ "$CFG" = c2 ] || exit 0

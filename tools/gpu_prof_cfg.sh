@@ -3,7 +3,7 @@
 T=$1; CFG=$2; shift 2
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; O=$ROOT/gpurun_out/$T; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $ROOT/bench.py --config $CFG --no-cpu-baseline "$@" > $O/prof.log 2>&1 || exit 1
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $ROOT/bench.py --full --config $CFG --no-cpu-baseline "$@" > $O/prof.log 2>&1 || exit 1
 python3 $ROOT/tools/bench_line.py $O/prof.log $CFG
 f=$(find $O/prof -name '*kernel_stats.csv' | head -n 1); python3 - "$f" <<'PY'
 import csv, sys

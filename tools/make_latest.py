@@ -58,7 +58,7 @@ def main(tag, config, cmd=None):
                 if steps:
                     k["valu_insts_per_step"] = v["valu_insts"] * v["calls"] / steps
             kernels[kind] = k
-    cmd = cmd or f"python bench.py --config {config}"
+    cmd = cmd or f"python bench.py --full --config {config}"
     path = os.path.join(ROOT, "profiles", "latest.json")
     try:
         out = json.load(open(path))
