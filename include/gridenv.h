@@ -67,7 +67,8 @@ typedef struct gw_config {
                                    at reset.  Everything else is shared.                    */
 } gw_config;
 
-/* Per-step outputs: device pointers, any may be NULL (not written). */
+/* Per-step outputs: device pointers, any may be NULL (not written).  New outputs are appended
+ * at the end: every existing field keeps its offset (fear_row is the latest, after desc_copy). */
 typedef struct gw_step_out {
     float *obs;          /* [K][E][H*W] obs after the step (reset obs if auto-reset)  */
     float *final_obs;    /* [K][E][H*W] terminal obs; rows written only for done envs */
@@ -103,6 +104,11 @@ typedef struct gw_step_out {
                             (gw_obs_view's layout; e.g. a descriptor replay ring's slot,
                             include/rollout_ops.h gw_replay_gather_desc); the terminal half
                             (words 8-11) only for envs that ended                         */
+    double *fear_row;    /* [E][K][N]  Resp[k][j] of FeAR_4_one_actor(actor = k)
+                            (custom/Responsibility.py:135-210): the row whose np.sum is
+                            `fear`[e][k]; 0.0 at j == k, for an actor that plays its MdR, and
+                            everywhere with FeAR off.  The step's pre-reset joint action, as
+                            `fear`; a FeAR-owned output (gw_set_obs_async | 4: gw_fear_fence)  */
 } gw_step_out;
 
 #define GW_STATS 8
@@ -265,7 +271,7 @@ gw_status gw_step_patch_next(void *env, int32_t P, float *patch, float *final_pa
  * enable | 4 (defer path, FeAR on): `stream` joins only the world update; fear_v2 (fear,
  * shaped, ep_return, ep_fear, the FeAR stats rows, score / fear_score) finishes on the internal
  * stream and overlaps the caller's next work (an actor that needs only the descriptors and
- * masks); those outputs are ready on `stream` after gw_fear_fence (gw_reset, gw_copy_state
+ * masks); those outputs, and fear_row, are ready on `stream` after gw_fear_fence (gw_reset, gw_copy_state
  * and the next gw_step order themselves).
  * Both kernel paths pipeline (defer: the writer on its own streams; merged: one step_obs launch). */
 gw_status gw_set_obs_async(void *env, int enable);

@@ -114,6 +114,14 @@ gw_status gw_replay_gather_desc(const gw_obs_source *src, const uint32_t *desc, 
 gw_status gw_eval_accum(const int32_t *crashes, const int32_t *apples, const double *fear, const uint8_t *done,
                         uint8_t *active, int64_t *counts, double *fear_total, int64_t E, int32_t K, void *stream);
 
+/* Per-pair responsibility totals of one step (gw_step_out.fear_row, [E][K][N] f64):
+ * totals[k][j] += sum over e (active[e] != 0, or all if active == NULL) of fear_row[e][k][j];
+ * *steps += 1.  Fixed summation order (e ascending per lane stride, then a fixed tree):
+ * deterministic.  One block, graph-capturable, no host sync.  Call it before gw_eval_accum in an
+ * evaluation step (that op retires the done envs from `active`). */
+gw_status gw_fear_row_accum(const double *fear_row, const uint8_t *active, int64_t E, int32_t K, int32_t N,
+                            double *totals, int64_t *steps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1377,21 +1377,34 @@ __device__ __forceinline__ void fear_task(const Params &p, Sh &sh, uint32_t tk, 
 }
 
 // FeAR phase C of one env: V counts -> Resp table -> np.sum of the Resp row in numpy's order.
+// The Resp row itself goes to gw_step_out.fear_row[e][k][.] when that output is set (uniform per
+// launch): an explicit zero row for an actor the de-duplication skipped (act == MdR: the
+// reference's vm == va there, Resp = 0.0).
 template <int N, int KMAX, class Sh>
-__device__ __forceinline__ void fear_values(const Params &p, const Sh &sh, int el, const int (&act)[N],
+__device__ __forceinline__ void fear_values(const Params &p, const Sh &sh, int el, int64_t e, const int (&act)[N],
                                             const int (&mdr)[N], const double *resp_s, double (&fear)[MAXN]) {
 #pragma unroll
     for (int k = 0; k < MAXN; ++k) fear[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        if (k >= p.K || act[k] == mdr[k]) continue;
+        if (k >= p.K) continue;
+        double *row = p.out.fear_row ? p.out.fear_row + (e * p.K + k) * N : nullptr;
+        if (act[k] == mdr[k]) {
+            if (row)
+#pragma unroll
+                for (int jj = 0; jj < N; ++jj) row[jj] = 0.0;
+            continue;
+        }
         const uint32_t cl = sh.close[el][k];
         const uint32_t b0 = sh.base[el][k][0], b1 = sh.base[el][k][1];
         double resp[N];
 #pragma unroll
         for (int jj = 0; jj < N; ++jj) {
             resp[jj] = 0.0;
-            if (jj == k) continue;
+            if (jj == k) {
+                if (row) row[jj] = 0.0;
+                continue;
+            }
             int vm, va;
             if ((cl >> jj) & 1u) {
                 vm = 0;
@@ -1405,6 +1418,7 @@ __device__ __forceinline__ void fear_values(const Params &p, const Sh &sh, int e
                 va = 9 * (int)((b1 >> jj) & 1u);
             }
             resp[jj] = resp_s[vm * 10 + va];
+            if (row) row[jj] = resp[jj];
         }
         fear[k] = np_sum_row<N>(resp, k);
     }
@@ -1581,7 +1595,7 @@ __device__ __forceinline__ void step_v2_block(const Params &p, int64_t bid, V2Sh
                 fin[n] = sh.fin[tid][n];
             }
             double fear[MAXN];
-            fear_values<N, KMAX>(p, sh, tid, act, mdr, resp_s, fear);
+            fear_values<N, KMAX>(p, sh, tid, e, act, mdr, resp_s, fear);
             const uint32_t bits = sh.bits[tid];
             ObsInfo<N> oi;
             finish_env<N>(p, e, es, act, mdr, fear, bits & 0xFFu, (bits >> 8) & 0xFFu, fin, bits >> 16, ct, oi, ctab);
@@ -1637,6 +1651,10 @@ __device__ __forceinline__ void step_v2_block(const Params &p, int64_t bid, V2Sh
             for (int k = 0; k < MAXN; ++k) fear[k] = 0.0;
             ObsInfo<N> oi;
             finish_env<N, DEFER>(p, e, es, act, mdr, fear, w.crash, w.restr, fin, caught, ct, oi, ctab);
+            if (!DEFER && p.out.fear_row) {  // FeAR off: zeros, as `fear` (deferred FeAR: fear_v2's)
+                double *row = p.out.fear_row + e * K * N;
+                for (int i = 0; i < K * N; ++i) row[i] = 0.0;
+            }
             STEP_STAMP(4);
             store_desc<N>(p, e, oi);
         }
@@ -1745,7 +1763,7 @@ __device__ __forceinline__ void fear_block(const Params &p, uint32_t bid) {
     if (tid < nenv) {
         const int64_t e = e0 + tid;
         double fear[MAXN];
-        fear_values<N, KMAX>(p, sh, tid, act, mdr, resp_s, fear);
+        fear_values<N, KMAX>(p, sh, tid, e, act, mdr, resp_s, fear);
         double shaped[MAXN], fsum_in[MAXN];
 #pragma unroll
         for (int k = 0; k < MAXN; ++k) {

@@ -404,6 +404,44 @@ __global__ void __launch_bounds__(EV_T) eval_accum_kernel(const int32_t *__restr
     }
 }
 
+// ---- per-pair responsibility totals (gw_step_out.fear_row summed over the envs): one block --------
+// F = K * N fields; lane group g = tid / F sums envs g, g + G, ... of field tid % F (U loads in
+// flight per lane, added in env order: a wave reads consecutive doubles), then the G group sums of
+// each field meet in a fixed binary tree, as tick_kernel's: deterministic
+constexpr int FR_T = 1024, FR_U = 8;
+
+__global__ void __launch_bounds__(FR_T) fear_row_accum_kernel(const double *__restrict__ rows,
+                                                              const uint8_t *__restrict__ active, int64_t E, int nf,
+                                                              double *__restrict__ totals, int64_t *__restrict__ steps) {
+    __shared__ double part[FR_T];
+    const int tid = threadIdx.x, groups = FR_T / nf, g = tid / nf, f = tid % nf;
+    double s = 0.0;
+    if (g < groups) {
+        for (int64_t e0 = g; e0 < E; e0 += (int64_t)FR_U * groups) {
+            double v[FR_U];
+#pragma unroll
+            for (int u = 0; u < FR_U; ++u) {
+                const int64_t e = e0 + (int64_t)u * groups;
+                v[u] = (e < E && (!active || active[e])) ? rows[e * nf + f] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < FR_U; ++u) s = __dadd_rn(s, v[u]);
+        }
+    }
+    part[tid] = s;
+    __syncthreads();
+    int pow2 = 1;
+    while (pow2 * 2 <= groups) pow2 *= 2;
+    if (g >= pow2 && g < groups) part[(g - pow2) * nf + f] = __dadd_rn(part[(g - pow2) * nf + f], s);
+    __syncthreads();
+    for (int stride = pow2 / 2; stride >= 1; stride /= 2) {
+        if (g < stride) part[g * nf + f] = __dadd_rn(part[g * nf + f], part[(g + stride) * nf + f]);
+        __syncthreads();
+    }
+    if (tid < nf) totals[tid] = __dadd_rn(totals[tid], part[tid]);
+    if (tid == 0 && steps) steps[0] += 1;
+}
+
 // ---- the packed per-step return gather (parallel.ReturnGather, world > 1) ----
 // Sender: this step's completed-episode returns (done envs, env order) are appended to a FIFO;
 // the send slot carries a 32-byte header {count, sent, backlog after, overflow} and the FIFO's
@@ -760,6 +798,22 @@ gw_status gw_eval_accum(const int32_t *crashes, const int32_t *apples, const dou
     hipLaunchKernelGGL(eval_accum_kernel, dim3(1), dim3(EV_T), 0, static_cast<hipStream_t>(stream), crashes, apples,
                        fear, done, active, counts, fear_total, E, (int)K);
     return hipGetLastError() == hipSuccess ? GW_OK : GW_ERR_HIP;
+}
+
+gw_status gw_fear_row_accum(const double *fear_row, const uint8_t *active, int64_t E, int32_t K, int32_t N,
+                            double *totals, int64_t *steps, void *stream) {
+    if (!fear_row || !totals || !steps || E < 0 || K < 1 || N < K || N > GW_MAX_AGENTS) {
+        gw_set_last_error("gw_fear_row_accum: bad argument");
+        return GW_ERR_ARG;
+    }
+    hipLaunchKernelGGL(fear_row_accum_kernel, dim3(1), dim3(FR_T), 0, static_cast<hipStream_t>(stream), fear_row,
+                       active, E, (int)(K * N), totals, steps);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gw_set_last_error((std::string("gw_fear_row_accum: ") + hipGetErrorString(e)).c_str());
+        return GW_ERR_HIP;
+    }
+    return GW_OK;
 }
 
 }  // extern "C"

@@ -154,7 +154,7 @@ class GwConfig(C.Structure):
 STEP_OUT_FIELDS = ["obs", "final_obs", "reward", "fear", "shaped", "term", "trunc", "done", "mask",
                    "crashes", "apples", "ep_return", "ep_fear", "ep_len", "actions", "mdr",
                    "final_pos", "crash_bits", "restr_bits", "stats", "done_copy", "stats_acc", "tick",
-                   "desc_copy"]
+                   "desc_copy", "fear_row"]
 GW_STATS = 8
 STATS_NAMES = ["done_return", "episodes", "fear", "crashes", "apples", "shaped", "done_len", "env_steps"]
 
@@ -186,7 +186,7 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_gather_pack_scratch", "gw_gather_pack", "gw_gather_unpack_plan_cap", "gw_gather_unpack",
            "gw_adam_soft_step", "gw_obs_desc_copy", "gw_replay_gather_desc",
            "gw_maddpg_desc_workspace_floats", "gw_maddpg_desc_prime", "gw_maddpg_desc_update", "gw_count_sims",
-           "gw_actor_images_view", "gw_maddpg_desc_update_img"]
+           "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum"]
 
 
 class GwObsSource(C.Structure):
@@ -332,6 +332,8 @@ def _declare(L):
     L.gw_mean_loss_bwd.restype = C.c_int
     L.gw_eval_accum.argtypes = [p] * 7 + [C.c_int64, C.c_int32, p]
     L.gw_eval_accum.restype = C.c_int
+    L.gw_fear_row_accum.argtypes = [p, p, C.c_int64, C.c_int32, C.c_int32, p, p, p]
+    L.gw_fear_row_accum.restype = C.c_int
     L.gw_affine_relu_fwd.argtypes = [p, p, p, p, C.c_int32, C.c_int64, C.c_int32, p]
     L.gw_affine_relu_fwd.restype = C.c_int
     L.gw_affine_relu_bwd.argtypes = [p] * 7 + [C.c_int32, C.c_int64, C.c_int32, p]

@@ -29,13 +29,16 @@ from .vec_env import VecGridEnv
 @torch.no_grad()
 def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, max_steps: int = 150,
              fear: bool = False, seed: int = 42, record_actions: bool = False, fused: bool | None = None,
-             variant: int = 0) -> dict:
+             variant: int = 0, resp_matrix: bool = False) -> dict:
+    """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
+    matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
+    restricted agent j) summed over the episodes still running and divided by "steps"."""
     sc = builtin(scenario) if isinstance(scenario, str) else scenario
     if fused is None:
         fused = actors.fusable(SimpleNamespace(K=sc.K, H=sc.H, W=sc.W))
     # the fused actor reads the obs descriptors: no dense obs is written at all
     env = VecGridEnv(sc, num_envs=episodes, fear=fear, max_steps=max_steps, auto_reset=False, seed=seed,
-                     obs=not fused, variant=variant)
+                     obs=not fused, variant=variant, fear_rows=resp_matrix)
     try:
         obs, mask = env.reset()
         dev = env.device
@@ -43,6 +46,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         counts = torch.zeros(3, dtype=torch.int64, device=dev)       # crashes, apples, steps
         fear_sum = torch.zeros(1, dtype=torch.float64, device=dev)
         lib = _lib.load()
+        resp = torch.zeros((env.K, env.N), dtype=torch.float64, device=dev) if resp_matrix else None
+        resp_calls = torch.zeros((), dtype=torch.int64, device=dev)
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):
@@ -53,6 +58,10 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             if record_actions:
                 recorded.append(actions.clone())
             r = env.step(actions)
+            if resp_matrix:  # the active envs' Resp rows, before gw_eval_accum retires the done ones
+                _lib.check(lib.gw_fear_row_accum(r.fear_row.data_ptr(), active.data_ptr(), episodes, env.K, env.N,
+                                                 resp.data_ptr(), resp_calls.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "gw_fear_row_accum")
             # the active envs' crashes, apples, steps and FeAR summed, then the done ones retired
             _lib.check(lib.gw_eval_accum(r.crashes.data_ptr(), r.apples.data_ptr(), r.fear.data_ptr(),
                                          r.done.data_ptr(), active.data_ptr(), counts.data_ptr(), fear_sum.data_ptr(),
@@ -66,6 +75,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
                 break
         c = counts.tolist()
         out = {"episodes": episodes, "crashes": c[0], "apples_caught": c[1], "steps": c[2], "fear": float(fear_sum)}
+        if resp_matrix:
+            out["resp"] = (resp / max(c[2], 1)).cpu()
         if record_actions:
             # the early-stop check runs every 8 steps: keep the actions up to the first step after
             # which every episode had ended (the steps an env-at-a-time loop would have taken)

@@ -179,7 +179,7 @@ class Rollout:
     def __init__(self, env: VecGridEnv, actors: MultiAgentActors | None = None, replay_slots: int = 0,
                  training: bool = True, group=None, seed: int = 0, fused: bool | None = None,
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
-                 patch_async: bool | None = None, desc_ring: bool = False):
+                 patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -200,7 +200,11 @@ class Rollout:
         step's actor (``fence()`` orders the ring slots).
         desc_ring (full-grid obs, GPU): the ring also keeps every step's obs descriptors and the
         learner samples from them (``ReplayRing(desc=True)``; ``learn_fence()`` then skips the
-        obs-writer wait, so the writer of step t overlaps the updates that follow it)."""
+        obs-writer wait, so the writer of step t overlaps the updates that follow it).
+        resp_matrix (an env built with ``fear_rows=True``): every step's per-pair responsibility rows
+        (StepResult.fear_row) are summed over the envs into a running [K, N] total
+        (gw_fear_row_accum, one launch per step, also inside ``capture`` graphs); ``totals()`` then
+        carries "resp" and "resp_steps"."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -259,6 +263,12 @@ class Rollout:
             raise ValueError("ReturnGather shard size != env.E")
         env.set_obs_async(obs_async, fear_async=fear_async)
         self._pending = None  # (stats, tick) of a step whose FeAR may still be in flight
+        self._resp = self._resp_steps = None
+        if resp_matrix:
+            if env.out.get("fear_row") is None:
+                raise ValueError("Rollout(resp_matrix=True) needs VecGridEnv(fear_rows=True)")
+            self._resp = torch.zeros((env.K, env.N), dtype=torch.float64, device=env.device)
+            self._resp_steps = torch.zeros((), dtype=torch.int64, device=env.device)
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0
@@ -277,6 +287,12 @@ class Rollout:
             self._reduce(stats, tick)
 
     def _reduce(self, stats, tick):
+        if self._resp is not None:  # the step's Resp rows (FeAR-owned: fenced by the caller) into the total
+            env = self.env
+            _lib.check(env.lib.gw_fear_row_accum(env.out["fear_row"].data_ptr(), None, env.E, env.K, env.N,
+                                                 self._resp.data_ptr(), self._resp_steps.data_ptr(),
+                                                 torch.cuda.current_stream(env.device).cuda_stream),
+                       "gw_fear_row_accum")
         if self.gather is not None:
             self.gather.push()  # the step wrote ep_return / done into the gather's send buffer
         if self._acc is not None:
@@ -541,14 +557,25 @@ class Rollout:
     def totals(self) -> dict:
         """Episode statistics summed over all steps (and ranks): completed-episode return sum,
         episodes, FeAR, crashes, apples, shaped reward, completed-episode length sum, env-steps.
-        With several ranks this is a collective (one all-reduce of 8 doubles): every rank calls it."""
-        if self._acc is None:
+        With ``resp_matrix``: "resp", the [K, N] sum of every step's and env's responsibility rows
+        (f64 CPU tensor), and "resp_steps", the steps it covers.
+        With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
+        the responsibility total): every rank calls it."""
+        if self._acc is None and self._resp is None:
             return {}
         self._flush()
-        local = self._acc.sum(0)
+        nst = _lib.GW_STATS if self._acc is not None else 0
+        parts = [self._acc.sum(0)] if nst else []
+        if self._resp is not None:  # all-reduced with the other statistics, in the same collective
+            parts.append(self._resp.reshape(-1))
+        local = torch.cat(parts) if len(parts) > 1 else parts[0].clone()  # (the all-reduce is in place)
         if self.distributed:
             dist.all_reduce(local, group=self.group)
-        return dict(zip(_lib.STATS_NAMES, local.cpu().tolist()))
+        out = dict(zip(_lib.STATS_NAMES, local[:nst].cpu().tolist()))
+        if self._resp is not None:
+            out["resp"] = local[nst:].reshape(self.env.K, self.env.N).cpu()
+            out["resp_steps"] = int(self._resp_steps)  # this rank's steps (the ranks step in lockstep)
+        return out
 
     def completed_scores(self, last: int | None = None):
         """The completed-episode returns of every rank, oldest first (``completed_episode_scores``

@@ -14,6 +14,8 @@ Layouts (device tensors, owned by the env and overwritten by the next call):
   crashes, apples, ep_len   [E] int32;  ep_return, ep_fear [E] float64
   debug outputs (debug=True): actions/mdr/final_pos [E, N] int32, crash_bits/restr_bits [E] uint8
   stats (stats=True): [rows, 8] float64 per-block partial sums of the step (_lib.STATS_NAMES)
+  fear_row (fear_rows=True): [E, K, N] float64, Resp[k][j] of FeAR_4_one_actor(actor = k): how much RL
+             agent k restricted agent j this step (its np.sum is fear[e, k]; zeros with FeAR off)
 """
 from __future__ import annotations
 
@@ -54,6 +56,7 @@ class StepResult:
     stats_acc: torch.Tensor | None = None  # running per-block totals (step(into=...))
     tick: torch.Tensor | None = None       # += 1 per step (step(into=...))
     desc_copy: torch.Tensor | None = None  # [E, 12] int32 copy of the obs descriptors (step(into=...))
+    fear_row: torch.Tensor | None = None   # [E, K, N] per-pair responsibility rows (fear_rows=True)
 
 
 class StepGraph:
@@ -80,7 +83,7 @@ class VecGridEnv:
                  fear_weight: float = -5.0, max_steps: int = 150, auto_reset: bool = True, seed: int = 42,
                  device: torch.device | int | None = None, env_offset: int = 0, final_obs: bool = False,
                  debug: bool = False, obs: bool = True, stats: bool = False, variant: int | str = 0,
-                 obs_dtype: torch.dtype = torch.float32):
+                 obs_dtype: torch.dtype = torch.float32, fear_rows: bool = False):
         if not torch.cuda.is_available():
             raise _lib.GwError("VecGridEnv needs a HIP device (no CPU fallback by design)")
         sc = builtin(scenario) if isinstance(scenario, str) else scenario
@@ -144,6 +147,7 @@ class VecGridEnv:
             restr_bits=torch.zeros(E, dtype=torch.uint8, device=dev) if debug else None,
             stats=torch.zeros((int(self.lib.gw_stats_rows(self.handle)), _lib.GW_STATS), **f64) if stats else None,
             done_copy=None, stats_acc=None, tick=None, desc_copy=None,
+            fear_row=torch.zeros((E, K, N), **f64) if fear_rows else None,
         )
         self._step_out = _lib.GwStepOut(*[_ptr(self.out[n]) for n in _lib.STEP_OUT_FIELDS])
         self._into_cache = {}  # step(): (GwStepOut, fields, StepResult) per set of destination buffers
@@ -178,7 +182,7 @@ class VecGridEnv:
                   "term": (torch.uint8, "EK"), "trunc": (torch.uint8, "EK"), "done": (torch.uint8, "E"),
                   "done_copy": (torch.uint8, "E"), "stats_acc": (torch.float64, "ROWS"),
                   "tick": (torch.int64, "ONE"), "desc_copy": (torch.int32, "DESC"),
-                  "ep_return": (torch.float64, "E")}
+                  "ep_return": (torch.float64, "E"), "fear_row": (torch.float64, "EKN")}
 
     def step(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
              spawn: torch.Tensor | None = None, obs_out: torch.Tensor | None = None,
@@ -189,7 +193,7 @@ class VecGridEnv:
         obs_out / final_obs_out: [K, E, H, W] float32 buffers to write this step's obs into
         instead of the env's own (e.g. a replay-ring slot: zero-copy replay storage);
         into: the same for any of obs, final_obs, reward, fear, shaped, term, trunc, done,
-        done_copy (a second destination of done), ep_return, stats_acc (per-block rows every
+        done_copy (a second destination of done), ep_return, fear_row, stats_acc (per-block rows every
         step ADDS to: a running total), tick (int64 scalar, += 1 per step) (contiguous tensors of
         the output's dtype and size; e.g. the send buffer of parallel.ReturnGather)."""
         rl = self._as_i32(rl_actions, (self.E, self.K))
@@ -230,7 +234,7 @@ class VecGridEnv:
             sizes = self._into_sizes
             if sizes is None:
                 sizes = self._into_sizes = {"KEHW": self.K * self.E * self.H * self.W, "EK": self.E * self.K,
-                                            "E": self.E, "ONE": 1, "DESC": self.E * 12,
+                                            "E": self.E, "ONE": 1, "DESC": self.E * 12, "EKN": self.E * self.K * self.N,
                                             "ROWS": int(self.lib.gw_stats_rows(self.handle)) * _lib.GW_STATS}
             for name, t in over.items():
                 dt, shp = self._INTO_SPEC[name]
@@ -397,7 +401,7 @@ class VecGridEnv:
         enable="lazy": the writer is launched at the next step, behind the caller's work between
         the steps (an actor kernel), instead of right after the world update.
         fear_async (defer path, FeAR on): the FeAR-owned outputs (fear, shaped, ep_return,
-        ep_fear, the FeAR stats rows) are ready only after ``fear_fence()``, so the caller's next
+        ep_fear, fear_row, the FeAR stats rows) are ready only after ``fear_fence()``, so the caller's next
         work (the fused actor) overlaps the FeAR kernel."""
         mode = 2 if enable == "lazy" else int(bool(enable))
         if mode and fear_async:
