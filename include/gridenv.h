@@ -159,14 +159,16 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * gw_patch_actor_act, gw_cnn_act, gw_patch_cnn_act), GW_SPAN_CNN_L1 the CNN heads' layer-1
  * listing kernel, GW_SPAN_CNN_LIST their bucket scan + unit plan and scatter (two launches), GW_SPAN_CNN_RARE
  * their recompute of the listed conv positions, GW_SPAN_WINDOW the window writer (gw_obs_patch),
- * GW_SPAN_LEARN one whole descriptor-learner update (gw_maddpg_desc_update's four launches).
+ * GW_SPAN_LEARN one whole descriptor-learner update (gw_maddpg_desc_update's four launches),
+ * GW_SPAN_FEAR_ALT the per-action FeAR table's kernel (fear_alt_kernel, gw_set_fear_alt).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
  * gw_step calls timed, and clears every span.  Used by bench.py for the live roofline. */
 enum {
     GW_SPAN_STEP = 0, GW_SPAN_OBS = 1, GW_SPAN_FEAR = 2, GW_SPAN_ACT = 3, GW_SPAN_CNN_L1 = 4,
-    GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8
+    GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8,
+    GW_SPAN_FEAR_ALT = 9
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -242,6 +244,19 @@ gw_status gw_obs_desc_copy(void *env, uint32_t *dst, void *stream);
  * its task count to *counter (device uint64, one atomic per block per step).  counter NULL: stop
  * counting (the default).  bench.py reports sims/s from it beside the VALU roofline. */
 gw_status gw_count_sims(void *env, uint64_t *counter);
+
+/* Every following gw_step also writes fear_alt [E][K][9] f64 (NULL: off, the default):
+ * fear_alt[e][k][a] = np.sum(Resp) of FeAR_4_one_actor(actor = k) on the step's pre-move world with
+ * the step's joint action, except that agent k plays a; k's close set and MdR as in the step.
+ * So fear_alt[e][k][actions[e][k]] == fear[e][k] and fear_alt[e][k][mdr[e][k]] == 0.0, bit for bit
+ * (the same Resp table and numpy-ordered sum); with FeAR off (cfg.fear == 0) the step stores zeros.
+ * It describes the pre-reset world of the step, as `fear`.  A FeAR-owned output: ordered on the
+ * caller's stream like `fear`, with gw_set_obs_async(| 4) ready after gw_fear_fence.  One more kernel
+ * per step (fear_alt_kernel: one wave per env, 9 (1 + 8 (c - 1)) world updates per actor with close
+ * count c), launched after the world update beside the obs writer; gw_count_sims counts its sims
+ * too.  The pointer is kept in the env (not in gw_step_out), so captured steps replay it.  May be
+ * called any time after gw_create; GW_ERR_ARG on a null env. */
+gw_status gw_set_fear_alt(void *env, double *fear_alt);
 
 /* Egocentric local patches of the env's last observation (an opt-in input format; the
  * reference observes the whole grid, ma_customenv.py:303-322): for every env and RL agent k the

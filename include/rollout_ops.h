@@ -122,6 +122,15 @@ gw_status gw_eval_accum(const int32_t *crashes, const int32_t *apples, const dou
 gw_status gw_fear_row_accum(const double *fear_row, const uint8_t *active, int64_t E, int32_t K, int32_t N,
                             double *totals, int64_t *steps, void *stream);
 
+/* Hindsight FeAR regret of one step (gw_set_fear_alt's table [E][K][9] f64 against the step's fear
+ * [E][K] f64):  totals [K][2] f64:  [k][0] += sum_e (fear[e][k] - min_a fear_alt[e][k][a]);
+ * [k][1] += #e with fear[e][k] == that minimum;  over envs with active[e] != 0 (NULL: all);
+ * *steps += 1.  The minimum runs over all nine actions (masking is the caller's business).  The same
+ * fixed summation order as gw_fear_row_accum: deterministic.  One block, graph-capturable, no host
+ * sync.  Call it before gw_eval_accum in an evaluation step. */
+gw_status gw_fear_regret_accum(const double *fear_alt, const double *fear, const uint8_t *active, int64_t E,
+                               int32_t K, double *totals, int64_t *steps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@
 #include "gridenv.h"
 #include "prof.h"
 #include "window_rows.h"
+#include "fear_alt_tasks.h"
 
 namespace gw {
 
@@ -96,7 +97,8 @@ struct Params {
     int obs_be;               // envs per obs_kernel block (<= OBS_BE)
     int obs_bf16;             // obs buffers hold bf16 (the merged step_obs kernel's writer role)
     int64_t e_begin, e_end;   // env range of this launch (step_v2 / obs_kernel chunks)
-    uint4 *fwork;             // [E][FearRec<N>::R4] deferred-FeAR records (GW_KERNEL=defer)
+    uint4 *fwork;             // [E][FearRec<N>::R4] deferred-FeAR records (GW_KERNEL=defer; inline FeAR:
+                              // only while gw_set_fear_alt is armed, else null)
     int64_t stats_row0;       // first gw_step_out.stats row this launch writes
     int variant;              // 0 CustomMAEnv, 1 single-agent CustomEnv (custom/customenv.py)
     int apples[MAXN];
@@ -678,7 +680,8 @@ __device__ __forceinline__ void finish_env(const Params &p, int64_t e, const Env
                                            const int (&act)[N], const int (&mdr)[N],
                                            const double (&fear)[MAXN], uint32_t crash,
                                            uint32_t restr, int (&fin)[N], uint32_t caught,
-                                           Contrib &ct, ObsInfo<N> &oi, const uint32_t *ctab = nullptr) {
+                                           Contrib &ct, ObsInfo<N> &oi, const uint32_t *ctab = nullptr,
+                                           bool rec = false) {  // rec: also store the FearRec (fear_alt armed)
     const int K = p.K;
     const uint32_t flags = es.flags;
     uint32_t apples = flags & 0xFFu, term = (flags >> 8) & 0xFFu, trunc = (flags >> 16) & 0xFFu;
@@ -768,7 +771,7 @@ __device__ __forceinline__ void finish_env(const Params &p, int64_t e, const Env
     if (!DEFER && o.ep_return) o.ep_return[e] = score;
     if (!DEFER && o.ep_fear) o.ep_fear[e] = fscore;
     if (o.ep_len) o.ep_len[e] = t;
-    if (DEFER) store_fear_rec<N>(p, e, es.pos, act, rew, bonus, done);
+    if (DEFER || rec) store_fear_rec<N>(p, e, es.pos, act, rew, bonus, done);
     if (o.crash_bits) o.crash_bits[e] = (uint8_t)crash;
     if (o.restr_bits) o.restr_bits[e] = (uint8_t)restr;
 #pragma unroll
@@ -1598,7 +1601,9 @@ __device__ __forceinline__ void step_v2_block(const Params &p, int64_t bid, V2Sh
             fear_values<N, KMAX>(p, sh, tid, e, act, mdr, resp_s, fear);
             const uint32_t bits = sh.bits[tid];
             ObsInfo<N> oi;
-            finish_env<N>(p, e, es, act, mdr, fear, bits & 0xFFu, (bits >> 8) & 0xFFu, fin, bits >> 16, ct, oi, ctab);
+            // inline FeAR with the fear_alt table armed (uniform per launch): the record fear_alt_kernel reads
+            finish_env<N>(p, e, es, act, mdr, fear, bits & 0xFFu, (bits >> 8) & 0xFFu, fin, bits >> 16, ct, oi, ctab,
+                          p.fwork != nullptr);
             store_desc<N>(p, e, oi);
         }
     } else {
@@ -1819,6 +1824,139 @@ __global__ void __launch_bounds__(128) fear_rows_kernel(Params p, PatchArgs a, u
 }
 
 // ---------------------------------------------------------------------------------------
+// fear_alt_kernel (gw_set_fear_alt): the per-action counterfactual FeAR table of a step,
+//   fear_alt[e][k][a] = np.sum(Resp) of FeAR_4_one_actor(actor = k) with k playing a,
+// from the step's FearRec (pre-step cells, joint action).  One wave per env, ALT_WAVES envs per
+// block; the env's tasks (csrc/fear_alt_tasks.h: per actor 9 variants x (1 base + 8 alternatives of
+// each close agent)) are dealt to the wave's lanes round-robin, one world update per lane and turn.
+// A sim ORs the affected agent's valid bit into the 9-bit set vb[k][a][j] (bit b = j valid under
+// its action b; the base sim supplies bit act[j], and all nine bits of an agent outside the close
+// set, which stays: 9 * valid(base) as fear_values); popcounts give the V counts.  The MdR variant
+// is one of the nine, so Resp[k][j](a) = tab[V(mdr[k], j)][V(a, j)], summed by np_sum_row.
+// Dynamic LDS: [cell table][Resp 100 f64].
+// ---------------------------------------------------------------------------------------
+constexpr int ALT_WAVES = 4, ALT_T = 64 * ALT_WAVES;
+
+template <int N>
+__global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__restrict__ table) {
+    constexpr bool LIST = N >= GW_LIST_MIN_N;
+    constexpr int VBW = fear_alt::bit_words(N, N);  // per env, sized for K = N
+    static_assert(fear_alt::max_per_env(4, 2) == 450 && fear_alt::max_per_env(8, 2) == 1026, "task maxima");
+    static_assert(VBW == N * NA * N && VBW <= 576, "valid-bit sets: [K <= N][9][N] words per env");
+    static_assert(fear_alt::max_per_env(N, N) <= 4104, "tasks per env fit an int with room");
+    __shared__ uint32_t vb[ALT_WAVES][VBW];
+    __shared__ uint2 wl[LIST ? ALT_T * N : 1];  // World<N, true> rows (one per thread)
+    __shared__ unsigned int s_nsim;
+    static_assert(sizeof(uint32_t) * ALT_WAVES * VBW + sizeof(uint2) * (LIST ? ALT_T * N : 1) <= 26 * 1024,
+                  "static LDS of fear_alt_kernel");
+    extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
+    uint32_t *ctab = reinterpret_cast<uint32_t *>(dyn + p.ctab_off);
+    double *resp_s = reinterpret_cast<double *>(dyn + p.resp_off);
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t e = p.e_begin + (int64_t)blockIdx.x * ALT_WAVES + wave;
+    const bool live = e < p.e_end;  // uniform per wave
+    const int K = min(p.K, N);
+    int pos[N], act[N], rew[MAXN];
+    uint32_t bonus = 0;
+    bool done = false;
+#pragma unroll
+    for (int n = 0; n < N; ++n) pos[n] = act[n] = 0;
+    if (live) load_fear_rec<N>(p, e, pos, act, rew, bonus, done);
+    lds_fill<ALT_T>(ctab, p.tb.celltab, p.HW, tid);
+    lds_fill<ALT_T>(reinterpret_cast<uint32_t *>(resp_s), reinterpret_cast<const uint32_t *>(p.tb.resp), 200, tid);
+    for (int i = lane; i < VBW; i += 64) vb[wave][i] = 0u;
+    if (tid == 0) s_nsim = 0u;
+    __syncthreads();
+    const CtabOk okv{ctab};
+
+    // the record's fields are clamped to their ranges before they index anything
+    int mdr[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        pos[n] = min(pos[n], p.HW - 1);
+        act[n] = min(act[n], NA - 1);
+        mdr[n] = min((int)((ctab[pos[n]] >> CT_MDR) & 0xFu), NA - 1);
+    }
+    // close sets (ma_customenv.py:456-464) and task counts of the actors, in registers
+    uint32_t close[N];
+    int tcount[N], ntask = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        close[k] = 0u;
+        tcount[k] = 0;
+        if (k >= K) continue;
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+            if (n == k || manhattan(p, pos[k], pos[n]) <= 5) close[k] |= 1u << n;
+        tcount[k] = fear_alt::per_actor(__popc(close[k]));  // popc in 1..N: at most 9 (1 + 8 (N - 1))
+        ntask += tcount[k];
+    }
+    if (!live) ntask = 0;
+    if (lane == 0 && p.sims && ntask) atomicAdd(&s_nsim, (unsigned int)ntask);
+
+    for (int ti = lane; ti < ntask; ti += 64) {
+        // (actor k, task r of k): the actors' tasks follow each other
+        int k = 0, r = ti;
+#pragma unroll
+        for (int q = 0; q < N - 1; ++q)
+            if (q == k && q < K - 1 && r >= tcount[q]) {
+                r -= tcount[q];
+                ++k;
+            }
+        uint32_t cl = 0u;
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+            if (q == k) cl = close[q];
+        const fear_alt::Task tk = fear_alt::decode(r, __popc(cl));
+        const int j = tk.slot < 0 ? -1 : fear_alt::nth_agent(cl & ~(1u << k), tk.slot);
+        int joint[N], fin[N], b = 0;
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            joint[n] = ((cl >> n) & 1u) ? act[n] : 0;
+            if (n == k) joint[n] = tk.a;
+            if (n == j) joint[n] = b = fear_alt::alternative(tk.bi, act[n]);
+        }
+        int apple[MAXN];
+#pragma unroll
+        for (int q = 0; q < MAXN; ++q) apple[q] = -1;
+        World<N, LIST> w;
+        w.init(pos, joint, p.W, p.w_magic);
+        if constexpr (LIST) w.lw = &wl[tid * N];
+        uint32_t caught;
+        simulate<N, true>(w, okv, 0, apple, caught, fin);
+        const uint32_t valid = ~(w.crash | w.restr) & ((1u << N) - 1u);
+        uint32_t *row = &vb[wave][(k * NA + tk.a) * N];
+        if (j >= 0) {
+            if ((valid >> j) & 1u) atomicOr(&row[j], 1u << b);
+        } else {
+#pragma unroll
+            for (int n = 0; n < N; ++n)
+                if (n != k && ((valid >> n) & 1u)) atomicOr(&row[n], ((cl >> n) & 1u) ? (1u << act[n]) : 0x1FFu);
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && p.sims && s_nsim) atomicAdd(p.sims, (unsigned long long)s_nsim);
+    if (!live) return;
+    // (k, a) per lane: V counts -> Resp table -> np.sum of the row in numpy's order
+    for (int i = lane; i < K * NA; i += 64) {
+        const int k = i / NA, a = i - k * NA;
+        int mk = 0;
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+            if (q == k) mk = mdr[q];
+        const uint32_t *rm = &vb[wave][(k * NA + mk) * N], *ra = &vb[wave][(k * NA + a) * N];
+        double resp[N];
+#pragma unroll
+        for (int jj = 0; jj < N; ++jj) {
+            const int vm = __popc(rm[jj] & 0x1FFu), va = __popc(ra[jj] & 0x1FFu);
+            resp[jj] = (jj == k) ? 0.0 : resp_s[vm * 10 + va];
+        }
+        table[(e * p.K + k) * NA + a] = np_sum_row<N>(resp, k);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Responsibility.FeAR (custom/Responsibility.py:57-132, every agent as actor) and FeAL
 // (:213-303) for n world snapshots, one 128-thread block per snapshot.  Every world update the
 // two need is one task (9 per group):  "act" groups jj = 0..N-1 (the action list unchanged,
@@ -2027,6 +2165,7 @@ struct Env {
     uint32_t *flags = nullptr, *episode = nullptr, *desc = nullptr;
     uint4 *fwork = nullptr;  // deferred-FeAR records (mode 3 with FeAR on)
     unsigned long long *sims = nullptr;  // gw_count_sims counter (device), or null
+    double *fear_alt = nullptr;  // gw_set_fear_alt table [E][K][9] (caller's device buffer), or null
     // gw_obs_patch's per-P tables of the map part of every window centre (patch_ops.hip MODE 4)
     std::vector<std::pair<int, float *>> ptbls;
     double *score = nullptr, *fscore = nullptr;
@@ -2269,7 +2408,8 @@ gw::Params make_params(const Env *env) {
     p.obs_bf16 = env->obs_bf16 ? 1 : 0;
     p.e_begin = 0;
     p.e_end = env->E;
-    p.fwork = env->fwork;
+    // the step kernels store records on the defer path; with inline FeAR only for an armed fear_alt
+    p.fwork = (env->mode == 3 && env->fear) || env->fear_alt ? env->fwork : nullptr;
     p.sims = env->sims;
     p.stats_row0 = 0;
     p.variant = env->variant;
@@ -2426,6 +2566,49 @@ hipError_t dispatch_fear(const Env *env, const gw::Params &p, hipStream_t s) {
         case 8: return launch_fear<8>(env, p, s);
     }
     return hipErrorInvalidValue;
+}
+
+template <int N>
+hipError_t launch_fear_alt(const Env *env, const gw::Params &p0, hipStream_t s) {
+    gw::Params p = p0;
+    p.lds_cdf = 0;  // dynamic LDS [cell table][Resp]
+    p.ctab_off = 0;
+    p.resp_off = ((env->HW * 4 + 15) / 16) * 16;
+    const int64_t n = p.e_end - p.e_begin;
+    if (n <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)((n + gw::ALT_WAVES - 1) / gw::ALT_WAVES);
+    const size_t dyn = (size_t)p.resp_off + 100 * sizeof(double);
+    gw_launch((gw::fear_alt_kernel<N>), dim3(grid), dim3(gw::ALT_T), dyn, s, p, env->fear_alt);
+    return hipGetLastError();
+}
+
+hipError_t dispatch_fear_alt(const Env *env, const gw::Params &p, hipStream_t s) {
+    switch (env->N) {
+        case 1: return launch_fear_alt<1>(env, p, s);
+        case 2: return launch_fear_alt<2>(env, p, s);
+        case 3: return launch_fear_alt<3>(env, p, s);
+        case 4: return launch_fear_alt<4>(env, p, s);
+        case 5: return launch_fear_alt<5>(env, p, s);
+        case 6: return launch_fear_alt<6>(env, p, s);
+        case 7: return launch_fear_alt<7>(env, p, s);
+        case 8: return launch_fear_alt<8>(env, p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// gw_set_fear_alt: the step's per-action FeAR table, after the world update (which stored the
+// FearRec) on the stream the step's FeAR runs on; FeAR off: zeros, as fear_row
+gw_status step_fear_alt(Env *env, const gw::Params &p, hipStream_t s) {
+    if (!env->fear_alt) return GW_OK;
+    if (!env->fear) {
+        HIP_TRY(hipMemsetAsync(env->fear_alt, 0, sizeof(double) * (size_t)env->E * env->K * GW_N_ACTIONS, s));
+        return GW_OK;
+    }
+    size_t b = 0;
+    if (env->profiling) GW_TRY(prof_span_begin(env, b));
+    HIP_TRY(dispatch_fear_alt(env, p, s));
+    if (env->profiling) GW_TRY(prof_span_end(env, b, GW_SPAN_FEAR_ALT));
+    return GW_OK;
 }
 
 template <int N>
@@ -2825,6 +3008,7 @@ static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int
         else
             HIP_TRY(dispatch_step(env, p, s));
         GW_TRY(span_end(s, b, merge ? 1 : 0));
+        GW_TRY(step_fear_alt(env, p, s));
         env->qobs = p;
         env->qobs_buf = nb;
         env->qobs_prof = env->profiling;
@@ -2869,6 +3053,7 @@ static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int
             GW_TRY(span_begin(ws, b));
             HIP_TRY(dispatch_fear(env, p, ws));
             GW_TRY(span_end(ws, b, 2));
+            GW_TRY(step_fear_alt(env, p, ws));  // a FeAR-owned output: behind gw_fear_fence
             HIP_TRY(hipEventRecord(env->fear_ev, ws));
             env->fear_pending = true;
         } else {
@@ -2877,6 +3062,7 @@ static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int
                 HIP_TRY(dispatch_fear(env, p, ws));
                 GW_TRY(span_end(ws, b, 2));
             }
+            GW_TRY(step_fear_alt(env, p, ws));
             if (on_aux) {
                 HIP_TRY(hipEventRecord(env->sync_ev[2], ws));  // join the world update + FeAR
                 HIP_TRY(hipStreamWaitEvent(s, env->sync_ev[2], 0));
@@ -2918,6 +3104,7 @@ static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int
                 HIP_TRY(dispatch_fear(env, p, s));
             }
             GW_TRY(span_end(s, b, 2));
+            GW_TRY(step_fear_alt(env, p, s));
             return GW_OK;
         }
         GW_TRY(ensure_aux(env, 2));
@@ -2926,6 +3113,7 @@ static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int
         GW_TRY(span_begin(env->aux, b));
         HIP_TRY(dispatch_fear(env, p, env->aux));
         GW_TRY(span_end(env->aux, b, 2));
+        GW_TRY(step_fear_alt(env, p, env->aux));  // beside the writer, as fear_v2
         GW_TRY(span_begin(s, b));
         HIP_TRY(launch_obs(env, p, p.out.obs, p.out.final_obs, s));
         GW_TRY(span_end(s, b, 1));
@@ -2937,6 +3125,7 @@ static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int
     GW_TRY(span_begin(s, b));
     HIP_TRY(dispatch_step(env, p, s));
     GW_TRY(span_end(s, b, 0));
+    GW_TRY(step_fear_alt(env, p, s));
     if (want_obs) {
         GW_TRY(span_begin(s, b));
         HIP_TRY(launch_obs(env, p, p.out.obs, p.out.final_obs, s));
@@ -3225,6 +3414,16 @@ static gw_status obs_patch_launch(Env *env, int32_t P, float *patch, float *fina
 gw_status gw_count_sims(void *handle, uint64_t *counter) {
     if (!handle) return fail(GW_ERR_ARG, "gw_count_sims: null env");
     static_cast<Env *>(handle)->sims = reinterpret_cast<unsigned long long *>(counter);
+    return GW_OK;
+}
+
+gw_status gw_set_fear_alt(void *handle, double *fear_alt) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_set_fear_alt: null env");
+    // the kernel reads the step's FearRec: the defer path owns the records already, the inline-FeAR
+    // paths get them on first use (the step kernels store them only while the table is armed)
+    if (fear_alt && env->fear && !env->fwork) GW_TRY(dalloc(env, &env->fwork, (size_t)env->E * (env->N <= 4 ? 1 : 2)));
+    env->fear_alt = fear_alt;
     return GW_OK;
 }
 

@@ -442,6 +442,53 @@ __global__ void __launch_bounds__(FR_T) fear_row_accum_kernel(const double *__re
     if (tid == 0 && steps) steps[0] += 1;
 }
 
+// ---- hindsight FeAR regret of one step (gw_set_fear_alt's table against the step's fear): one block ----
+// F = 2 K fields, field 2 k: fear[e][k] - min_a fear_alt[e][k][a], field 2 k + 1: 1.0 where fear[e][k]
+// is that minimum (counts stay exact in f64); the same lane groups, env order and tree as
+// fear_row_accum_kernel
+__global__ void __launch_bounds__(FR_T) fear_regret_accum_kernel(const double *__restrict__ alt,
+                                                                 const double *__restrict__ fear,
+                                                                 const uint8_t *__restrict__ active, int64_t E, int K,
+                                                                 double *__restrict__ totals,
+                                                                 int64_t *__restrict__ steps) {
+    __shared__ double part[FR_T];
+    const int nf = 2 * K;
+    const int tid = threadIdx.x, groups = FR_T / nf, g = tid / nf, f = tid % nf, k = f >> 1;
+    double s = 0.0;
+    if (g < groups) {
+        for (int64_t e0 = g; e0 < E; e0 += (int64_t)FR_U * groups) {
+            double v[FR_U];
+#pragma unroll
+            for (int u = 0; u < FR_U; ++u) {
+                const int64_t e = e0 + (int64_t)u * groups;
+                v[u] = 0.0;
+                if (e < E && (!active || active[e])) {
+                    const double *row = alt + (e * K + k) * 9;
+                    double m = row[0];
+#pragma unroll
+                    for (int a = 1; a < 9; ++a) m = row[a] < m ? row[a] : m;
+                    const double x = fear[e * K + k];
+                    v[u] = (f & 1) ? (x == m ? 1.0 : 0.0) : __dsub_rn(x, m);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < FR_U; ++u) s = __dadd_rn(s, v[u]);
+        }
+    }
+    part[tid] = s;
+    __syncthreads();
+    int pow2 = 1;
+    while (pow2 * 2 <= groups) pow2 *= 2;
+    if (g >= pow2 && g < groups) part[(g - pow2) * nf + f] = __dadd_rn(part[(g - pow2) * nf + f], s);
+    __syncthreads();
+    for (int stride = pow2 / 2; stride >= 1; stride /= 2) {
+        if (g < stride) part[g * nf + f] = __dadd_rn(part[g * nf + f], part[(g + stride) * nf + f]);
+        __syncthreads();
+    }
+    if (tid < nf) totals[tid] = __dadd_rn(totals[tid], part[tid]);
+    if (tid == 0 && steps) steps[0] += 1;
+}
+
 // ---- the packed per-step return gather (parallel.ReturnGather, world > 1) ----
 // Sender: this step's completed-episode returns (done envs, env order) are appended to a FIFO;
 // the send slot carries a 32-byte header {count, sent, backlog after, overflow} and the FIFO's
@@ -811,6 +858,22 @@ gw_status gw_fear_row_accum(const double *fear_row, const uint8_t *active, int64
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         gw_set_last_error((std::string("gw_fear_row_accum: ") + hipGetErrorString(e)).c_str());
+        return GW_ERR_HIP;
+    }
+    return GW_OK;
+}
+
+gw_status gw_fear_regret_accum(const double *fear_alt, const double *fear, const uint8_t *active, int64_t E,
+                               int32_t K, double *totals, int64_t *steps, void *stream) {
+    if (!fear_alt || !fear || !totals || !steps || E < 0 || K < 1 || K > GW_MAX_AGENTS) {
+        gw_set_last_error("gw_fear_regret_accum: bad argument");
+        return GW_ERR_ARG;
+    }
+    hipLaunchKernelGGL(fear_regret_accum_kernel, dim3(1), dim3(FR_T), 0, static_cast<hipStream_t>(stream), fear_alt,
+                       fear, active, E, (int)K, totals, steps);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gw_set_last_error((std::string("gw_fear_regret_accum: ") + hipGetErrorString(e)).c_str());
         return GW_ERR_HIP;
     }
     return GW_OK;

@@ -29,7 +29,8 @@ HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_op
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
-                                   os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "measure.h")]
+                                   os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "measure.h"),
+                                   os.path.join(CSRC, "fear_alt_tasks.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -186,7 +187,8 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_gather_pack_scratch", "gw_gather_pack", "gw_gather_unpack_plan_cap", "gw_gather_unpack",
            "gw_adam_soft_step", "gw_obs_desc_copy", "gw_replay_gather_desc",
            "gw_maddpg_desc_workspace_floats", "gw_maddpg_desc_prime", "gw_maddpg_desc_update", "gw_count_sims",
-           "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum"]
+           "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
+           "gw_set_fear_alt", "gw_fear_regret_accum"]
 
 
 class GwObsSource(C.Structure):
@@ -334,6 +336,10 @@ def _declare(L):
     L.gw_eval_accum.restype = C.c_int
     L.gw_fear_row_accum.argtypes = [p, p, C.c_int64, C.c_int32, C.c_int32, p, p, p]
     L.gw_fear_row_accum.restype = C.c_int
+    L.gw_set_fear_alt.argtypes = [p, p]
+    L.gw_set_fear_alt.restype = C.c_int
+    L.gw_fear_regret_accum.argtypes = [p, p, p, C.c_int64, C.c_int32, p, p, p]
+    L.gw_fear_regret_accum.restype = C.c_int
     L.gw_affine_relu_fwd.argtypes = [p, p, p, p, C.c_int32, C.c_int64, C.c_int32, p]
     L.gw_affine_relu_fwd.restype = C.c_int
     L.gw_affine_relu_bwd.argtypes = [p] * 7 + [C.c_int32, C.c_int64, C.c_int32, p]

@@ -29,16 +29,22 @@ from .vec_env import VecGridEnv
 @torch.no_grad()
 def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, max_steps: int = 150,
              fear: bool = False, seed: int = 42, record_actions: bool = False, fused: bool | None = None,
-             variant: int = 0, resp_matrix: bool = False) -> dict:
+             variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False) -> dict:
     """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
     matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
-    restricted agent j) summed over the episodes still running and divided by "steps"."""
+    restricted agent j) summed over the episodes still running and divided by "steps".
+    fear_regret (with ``fear=True``): the result also carries "fear_regret" [K], the policy's hindsight
+    FeAR regret fear[e, k] - min_a fear_alt[e, k, a] (StepResult.fear_alt, the minimum over all nine
+    actions) per active env-step, and "fear_best_frac" [K], how often agent k's action was
+    FeAR-minimal (f64 CPU tensors)."""
+    if fear_regret and not fear:
+        raise ValueError("evaluate(fear_regret=True) needs fear=True")
     sc = builtin(scenario) if isinstance(scenario, str) else scenario
     if fused is None:
         fused = actors.fusable(SimpleNamespace(K=sc.K, H=sc.H, W=sc.W))
     # the fused actor reads the obs descriptors: no dense obs is written at all
     env = VecGridEnv(sc, num_envs=episodes, fear=fear, max_steps=max_steps, auto_reset=False, seed=seed,
-                     obs=not fused, variant=variant, fear_rows=resp_matrix)
+                     obs=not fused, variant=variant, fear_rows=resp_matrix, fear_alt=fear_regret)
     try:
         obs, mask = env.reset()
         dev = env.device
@@ -48,6 +54,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         lib = _lib.load()
         resp = torch.zeros((env.K, env.N), dtype=torch.float64, device=dev) if resp_matrix else None
         resp_calls = torch.zeros((), dtype=torch.int64, device=dev)
+        regret = torch.zeros((env.K, 2), dtype=torch.float64, device=dev) if fear_regret else None
+        regret_calls = torch.zeros((), dtype=torch.int64, device=dev)
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):
@@ -62,6 +70,11 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
                 _lib.check(lib.gw_fear_row_accum(r.fear_row.data_ptr(), active.data_ptr(), episodes, env.K, env.N,
                                                  resp.data_ptr(), resp_calls.data_ptr(),
                                                  torch.cuda.current_stream(dev).cuda_stream), "gw_fear_row_accum")
+            if fear_regret:  # the active envs' regret, likewise before the done ones are retired
+                _lib.check(lib.gw_fear_regret_accum(r.fear_alt.data_ptr(), r.fear.data_ptr(), active.data_ptr(),
+                                                    episodes, env.K, regret.data_ptr(), regret_calls.data_ptr(),
+                                                    torch.cuda.current_stream(dev).cuda_stream),
+                           "gw_fear_regret_accum")
             # the active envs' crashes, apples, steps and FeAR summed, then the done ones retired
             _lib.check(lib.gw_eval_accum(r.crashes.data_ptr(), r.apples.data_ptr(), r.fear.data_ptr(),
                                          r.done.data_ptr(), active.data_ptr(), counts.data_ptr(), fear_sum.data_ptr(),
@@ -77,6 +90,9 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         out = {"episodes": episodes, "crashes": c[0], "apples_caught": c[1], "steps": c[2], "fear": float(fear_sum)}
         if resp_matrix:
             out["resp"] = (resp / max(c[2], 1)).cpu()
+        if fear_regret:
+            reg = (regret / max(c[2], 1)).cpu()
+            out["fear_regret"], out["fear_best_frac"] = reg[:, 0].clone(), reg[:, 1].clone()
         if record_actions:
             # the early-stop check runs every 8 steps: keep the actions up to the first step after
             # which every episode had ended (the steps an env-at-a-time loop would have taken)

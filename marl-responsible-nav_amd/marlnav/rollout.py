@@ -179,7 +179,8 @@ class Rollout:
     def __init__(self, env: VecGridEnv, actors: MultiAgentActors | None = None, replay_slots: int = 0,
                  training: bool = True, group=None, seed: int = 0, fused: bool | None = None,
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
-                 patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False):
+                 patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False,
+                 fear_regret: bool = False):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -204,7 +205,12 @@ class Rollout:
         resp_matrix (an env built with ``fear_rows=True``): every step's per-pair responsibility rows
         (StepResult.fear_row) are summed over the envs into a running [K, N] total
         (gw_fear_row_accum, one launch per step, also inside ``capture`` graphs); ``totals()`` then
-        carries "resp" and "resp_steps"."""
+        carries "resp" and "resp_steps".
+        fear_regret (an env built with ``fear_alt=True``): every step's hindsight FeAR regret,
+        fear[e, k] - min_a fear_alt[e, k, a], and the count of envs whose agent k took a FeAR-minimal
+        action are summed over the envs (gw_fear_regret_accum, one launch per step, also inside
+        ``capture`` graphs); ``totals()`` then carries "fear_regret" [K], "fear_best" [K] and
+        "fear_regret_steps"."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -269,6 +275,12 @@ class Rollout:
                 raise ValueError("Rollout(resp_matrix=True) needs VecGridEnv(fear_rows=True)")
             self._resp = torch.zeros((env.K, env.N), dtype=torch.float64, device=env.device)
             self._resp_steps = torch.zeros((), dtype=torch.int64, device=env.device)
+        self._regret = self._regret_steps = None
+        if fear_regret:
+            if env.out.get("fear_alt") is None:
+                raise ValueError("Rollout(fear_regret=True) needs VecGridEnv(fear_alt=True)")
+            self._regret = torch.zeros((env.K, 2), dtype=torch.float64, device=env.device)
+            self._regret_steps = torch.zeros((), dtype=torch.int64, device=env.device)
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0
@@ -293,6 +305,13 @@ class Rollout:
                                                  self._resp.data_ptr(), self._resp_steps.data_ptr(),
                                                  torch.cuda.current_stream(env.device).cuda_stream),
                        "gw_fear_row_accum")
+        if self._regret is not None:  # the step's per-action table against its fear (both FeAR-owned)
+            env = self.env
+            _lib.check(env.lib.gw_fear_regret_accum(env.out["fear_alt"].data_ptr(), env.out["fear"].data_ptr(), None,
+                                                    env.E, env.K, self._regret.data_ptr(),
+                                                    self._regret_steps.data_ptr(),
+                                                    torch.cuda.current_stream(env.device).cuda_stream),
+                       "gw_fear_regret_accum")
         if self.gather is not None:
             self.gather.push()  # the step wrote ep_return / done into the gather's send buffer
         if self._acc is not None:
@@ -559,22 +578,31 @@ class Rollout:
         episodes, FeAR, crashes, apples, shaped reward, completed-episode length sum, env-steps.
         With ``resp_matrix``: "resp", the [K, N] sum of every step's and env's responsibility rows
         (f64 CPU tensor), and "resp_steps", the steps it covers.
+        With ``fear_regret``: "fear_regret" [K] (the summed hindsight FeAR regret), "fear_best" [K] (env-steps
+        in which agent k's action was FeAR-minimal) and "fear_regret_steps".
         With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
         the responsibility total): every rank calls it."""
-        if self._acc is None and self._resp is None:
+        if self._acc is None and self._resp is None and self._regret is None:
             return {}
         self._flush()
         nst = _lib.GW_STATS if self._acc is not None else 0
         parts = [self._acc.sum(0)] if nst else []
         if self._resp is not None:  # all-reduced with the other statistics, in the same collective
             parts.append(self._resp.reshape(-1))
+        if self._regret is not None:
+            parts.append(self._regret.reshape(-1))
         local = torch.cat(parts) if len(parts) > 1 else parts[0].clone()  # (the all-reduce is in place)
         if self.distributed:
             dist.all_reduce(local, group=self.group)
         out = dict(zip(_lib.STATS_NAMES, local[:nst].cpu().tolist()))
         if self._resp is not None:
-            out["resp"] = local[nst:].reshape(self.env.K, self.env.N).cpu()
+            out["resp"] = local[nst:nst + self.env.K * self.env.N].reshape(self.env.K, self.env.N).cpu()
             out["resp_steps"] = int(self._resp_steps)  # this rank's steps (the ranks step in lockstep)
+            nst += self.env.K * self.env.N
+        if self._regret is not None:
+            reg = local[nst:nst + 2 * self.env.K].reshape(self.env.K, 2).cpu()
+            out["fear_regret"], out["fear_best"] = reg[:, 0].clone(), reg[:, 1].clone()
+            out["fear_regret_steps"] = int(self._regret_steps)
         return out
 
     def completed_scores(self, last: int | None = None):

@@ -16,6 +16,9 @@ Layouts (device tensors, owned by the env and overwritten by the next call):
   stats (stats=True): [rows, 8] float64 per-block partial sums of the step (_lib.STATS_NAMES)
   fear_row (fear_rows=True): [E, K, N] float64, Resp[k][j] of FeAR_4_one_actor(actor = k): how much RL
              agent k restricted agent j this step (its np.sum is fear[e, k]; zeros with FeAR off)
+  fear_alt (fear_alt=True): [E, K, 9] float64, the step's FeAR of RL agent k had it played action a while
+             everybody else did what they did (gw_set_fear_alt): fear_alt[e, k, actions[e, k]] is
+             fear[e, k] and fear_alt[e, k, mdr[e, k]] is 0.0, bit for bit; zeros with FeAR off
 """
 from __future__ import annotations
 
@@ -57,6 +60,7 @@ class StepResult:
     tick: torch.Tensor | None = None       # += 1 per step (step(into=...))
     desc_copy: torch.Tensor | None = None  # [E, 12] int32 copy of the obs descriptors (step(into=...))
     fear_row: torch.Tensor | None = None   # [E, K, N] per-pair responsibility rows (fear_rows=True)
+    fear_alt: torch.Tensor | None = None   # [E, K, 9] per-action counterfactual FeAR (fear_alt=True)
 
 
 class StepGraph:
@@ -83,7 +87,8 @@ class VecGridEnv:
                  fear_weight: float = -5.0, max_steps: int = 150, auto_reset: bool = True, seed: int = 42,
                  device: torch.device | int | None = None, env_offset: int = 0, final_obs: bool = False,
                  debug: bool = False, obs: bool = True, stats: bool = False, variant: int | str = 0,
-                 obs_dtype: torch.dtype = torch.float32, fear_rows: bool = False):
+                 obs_dtype: torch.dtype = torch.float32, fear_rows: bool = False,
+                 fear_alt: bool = False):
         if not torch.cuda.is_available():
             raise _lib.GwError("VecGridEnv needs a HIP device (no CPU fallback by design)")
         sc = builtin(scenario) if isinstance(scenario, str) else scenario
@@ -148,7 +153,11 @@ class VecGridEnv:
             stats=torch.zeros((int(self.lib.gw_stats_rows(self.handle)), _lib.GW_STATS), **f64) if stats else None,
             done_copy=None, stats_acc=None, tick=None, desc_copy=None,
             fear_row=torch.zeros((E, K, N), **f64) if fear_rows else None,
+            # not a gw_step_out field: the env keeps the pointer (gw_set_fear_alt), so it has no step(into=...)
+            fear_alt=torch.zeros((E, K, 9), **f64) if fear_alt else None,
         )
+        if fear_alt:
+            _lib.check(self.lib.gw_set_fear_alt(self.handle, _ptr(self.out["fear_alt"])), "gw_set_fear_alt")
         self._step_out = _lib.GwStepOut(*[_ptr(self.out[n]) for n in _lib.STEP_OUT_FIELDS])
         self._into_cache = {}  # step(): (GwStepOut, fields, StepResult) per set of destination buffers
         self._into_sizes = None  # the destination sizes step(into=...) checks (built on first use)
