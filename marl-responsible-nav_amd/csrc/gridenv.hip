@@ -2089,6 +2089,13 @@ gw_status fail(gw_status s, const std::string &msg) {
         if (_s != GW_OK) return _s;    \
     } while (0)
 
+// the two kernel paths (gw_create picks by batch size; GW_KERNEL=defer|merged forces); the values
+// are what gw_kernel_path() and PipeState.mode carry
+enum KernelPath : int {
+    PATH_DEFER = 3,   // FeAR on: step_v2 <DEFER>, then fear_v2 || obs_kernel; FeAR off: step_v2, then obs_kernel
+    PATH_MERGED = 4,  // synchronous as defer with FeAR inline; with async obs one step_obs launch per step
+};
+
 struct Env {
     int device = 0;
     int H = 0, W = 0, HW = 0, N = 0, K = 0, F = 0, P = 0;
@@ -2098,10 +2105,7 @@ struct Env {
     uint64_t seed = 0;
     int apples[GW_MAX_AGENTS] = {0};
     bool initialized = false;
-    int mode = 3;        // kernel path (gw_create picks by batch size; GW_KERNEL=defer|merged forces):
-                         // 3 "defer" (FeAR on: step_v2 <DEFER>, then fear_v2 || obs_kernel; FeAR off:
-                         // step_v2, then obs_kernel), 4 "merged" (synchronous as defer with FeAR
-                         // inline; with async obs one step_obs launch per step)
+    KernelPath mode = PATH_DEFER;
     int obs_be = 2;      // envs per obs_kernel block (default: see gw_create)
     bool obs_bf16 = false;  // gw_set_obs_dtype(env, GW_OBS_BF16): obs buffers hold bf16 (lossless)
     int obs_be_f32 = 2;         // the float32 writer's default
@@ -2163,7 +2167,7 @@ struct Env {
     // state
     int32_t *pos = nullptr, *t = nullptr, *prev = nullptr;
     uint32_t *flags = nullptr, *episode = nullptr, *desc = nullptr;
-    uint4 *fwork = nullptr;  // deferred-FeAR records (mode 3 with FeAR on)
+    uint4 *fwork = nullptr;  // deferred-FeAR records (defer path with FeAR on)
     unsigned long long *sims = nullptr;  // gw_count_sims counter (device), or null
     double *fear_alt = nullptr;  // gw_set_fear_alt table [E][K][9] (caller's device buffer), or null
     // gw_obs_patch's per-P tables of the map part of every window centre (patch_ops.hip MODE 4)
@@ -2174,7 +2178,7 @@ struct Env {
     bool profiling = false;
     std::vector<hipEvent_t> ev_pool;   // timing events, reused across calls
     size_t ev_used = 0;
-    struct Span { size_t b, e; int kind; };  // kind 0 = step kernel(s), 1 = obs kernel(s), 2 = fear_v2
+    struct Span { size_t b, e; int kind; };  // b, e: ev_pool indices; kind: a GW_SPAN_* value
     std::vector<Span> spans;
     int64_t steps_timed = 0;
     // flags of the pipeline's events.  They only order kernels of this device's queues (every
@@ -2187,7 +2191,9 @@ struct Env {
     // event) instead of a marker packet after it (+0.5 %, profiles/HISTORY.md)
 };
 
-// the second stream and n fork/join events (timing disabled), created on first use
+// deferred FeAR: the world update stores FearRec records and fear_v2 runs as its own launch
+bool defer_fear(const Env *env) { return env->mode == PATH_DEFER && env->fear; }
+
 // n fork/join events (timing disabled), created on first use
 gw_status ensure_events(Env *env, int n) {
     while ((int)env->sync_ev.size() < n) {
@@ -2212,8 +2218,7 @@ gw_status ensure_aux(Env *env, int n) {
 
 // the async-obs stream and its per-descriptor-buffer completion events, created on first use
 gw_status ensure_obs_stream(Env *env) {
-    const gw_status st = ensure_events(env, 3);
-    if (st != GW_OK) return st;
+    GW_TRY(ensure_events(env, 3));
     if (!env->obs_stream) HIP_TRY(hipStreamCreateWithFlags(&env->obs_stream, hipStreamNonBlocking));
     for (hipEvent_t &e : env->obs_done)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, env->sync_flags));
@@ -2237,84 +2242,6 @@ void gw_launch(F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args.
     gwprof::launch(kernel, grid, block, lds, s, args...);
 }
 
-hipError_t launch_obs(const Env *env, const gw::Params &p, float *obs, float *final_obs, hipStream_t s);
-hipEvent_t next_event(Env *env);
-gw_status prof_span_begin(Env *env, size_t &idx);
-gw_status prof_span_end(Env *env, size_t idx, int kind);
-void prof_span_split(Env *env, int kind);
-
-// launch the queued obs_kernel on the obs stream, after its world update and (after != null)
-// after the caller's work up to `after`
-gw_status flush_obs(Env *env, hipEvent_t after, hipStream_t on = nullptr) {
-    if (!env->obs_queued) return GW_OK;
-    if (env->mode == 4) {  // merged: the last step's writer alone, on `on` (default: that step's stream)
-        const bool prof = env->qobs_prof;
-        size_t b = 0;
-        if (prof && prof_span_begin(env, b) != GW_OK) return GW_ERR_HIP;
-        HIP_TRY(launch_obs(env, env->qobs, env->qobs.out.obs, env->qobs.out.final_obs, on ? on : env->last_stream));
-        if (prof) (void)prof_span_end(env, b, 1);
-        env->obs_queued = false;
-        return GW_OK;
-    }
-    // writers into the buffers of the last writer stay on its stream (write-after-write order);
-    // a writer into other buffers alternates to the other obs stream
-    const bool other = env->obs_streams > 1 && env->qobs.out.obs != env->obs_last[0] &&
-                       (env->qobs.out.final_obs == nullptr || env->qobs.out.final_obs != env->obs_last[1]);
-    if (other && !env->obs_stream2) HIP_TRY(hipStreamCreateWithFlags(&env->obs_stream2, hipStreamNonBlocking));
-    if (other) env->obs_cur ^= 1;
-    env->obs_last[0] = env->qobs.out.obs;
-    env->obs_last[1] = env->qobs.out.final_obs;
-    hipStream_t os = env->obs_cur ? env->obs_stream2 : env->obs_stream;
-    HIP_TRY(hipStreamWaitEvent(os, env->world_ev, 0));
-    if (after) HIP_TRY(hipStreamWaitEvent(os, after, 0));
-    const bool prof = env->qobs_prof;  // timed iff the step that queued it was
-    size_t b = 0;
-    if (prof && prof_span_begin(env, b) != GW_OK) return GW_ERR_HIP;
-    const bool bind = !prof;  // obs_done carried by the writer's launch
-    if (bind) t_bind_stop = env->obs_done[env->qobs_buf];
-    const hipError_t le = launch_obs(env, env->qobs, env->qobs.out.obs, env->qobs.out.final_obs, os);
-    t_bind_stop = nullptr;
-    HIP_TRY(le);
-    if (prof) (void)prof_span_end(env, b, 1);
-    if (!bind) HIP_TRY(hipEventRecord(env->obs_done[env->qobs_buf], os));
-    env->obs_pending[env->qobs_buf] = true;
-    env->obs_queued = false;
-    return GW_OK;
-}
-
-// make `s` wait for an async fear_v2 still in flight
-gw_status wait_fear(Env *env, hipStream_t s) {
-    if (env->fear_pending) HIP_TRY(hipStreamWaitEvent(s, env->fear_ev, 0));
-    return GW_OK;
-}
-
-// launch a queued obs_kernel and make `s` wait for every obs_kernel of the async-obs stream
-// (and for an async fear_v2: the callers rewrite state or descriptors in place)
-gw_status wait_obs(Env *env, hipStream_t s) {
-    {
-        const gw_status st = wait_fear(env, s);
-        if (st != GW_OK) return st;
-    }
-    if (env->obs_queued) {
-        if (env->mode == 4) {
-            // merged: the writer runs on s, after the step that queued it (a graph replay of
-            // captured steps runs on s itself; its capture stream holds no work)
-            if (env->last_stream != s) {
-                GW_TRY(ensure_events(env, 1));
-                HIP_TRY(hipEventRecord(env->sync_ev[0], env->last_stream));
-                HIP_TRY(hipStreamWaitEvent(s, env->sync_ev[0], 0));
-            }
-            GW_TRY(flush_obs(env, nullptr, s));
-        } else {
-            const gw_status st = flush_obs(env, nullptr);
-            if (st != GW_OK) return st;
-        }
-    }
-    for (int i = 0; i < 2; ++i)
-        if (env->obs_pending[i]) HIP_TRY(hipStreamWaitEvent(s, env->obs_done[i], 0));
-    return GW_OK;
-}
-
 hipEvent_t next_event(Env *env) {
     if (env->ev_used == env->ev_pool.size()) {
         hipEvent_t e = nullptr;
@@ -2325,12 +2252,12 @@ hipEvent_t next_event(Env *env) {
 }
 
 // a profiled span: two timing events handed to the span's kernel launches (gw_launch).  The open
-// span's first event index is also kept thread-locally, so a launch sequence can split it
+// span's first event index is kept thread-locally, so a launch sequence can split it
 // (prof_span_split: the obs writer's chunks are one span each, as a kernel trace counts them)
 thread_local size_t t_span_idx = 0;
 
-gw_status prof_span_begin(Env *env, size_t &idx) {
-    idx = env->ev_used;
+gw_status prof_span_begin(Env *env) {
+    const size_t idx = env->ev_used;
     hipEvent_t a = next_event(env), b = next_event(env);
     if (!a || !b) return fail(GW_ERR_HIP, "hipEventCreate failed");
     t_span_start = a;
@@ -2339,15 +2266,14 @@ gw_status prof_span_begin(Env *env, size_t &idx) {
     return GW_OK;
 }
 
-gw_status prof_span_end(Env *env, size_t idx, int kind) {
-    (void)idx;  // the span open now (a split may have replaced the one `idx` began)
+// close the span open now (a split may have replaced the one its begin opened)
+void prof_span_end(Env *env, int kind) {
     if (t_span_start) {  // no kernel was launched in the span: nothing to time
         env->ev_used = t_span_idx;
     } else {
         env->spans.push_back({t_span_idx, t_span_idx + 1, kind});
     }
     t_span_start = t_span_stop = nullptr;
-    return GW_OK;
 }
 
 // close the open span after the launches made so far and open the next one (no-op without an
@@ -2355,27 +2281,32 @@ gw_status prof_span_end(Env *env, size_t idx, int kind) {
 void prof_span_split(Env *env, int kind) {
     if (!t_span_stop || t_span_start) return;
     env->spans.push_back({t_span_idx, t_span_idx + 1, kind});
-    size_t idx = 0;
-    if (prof_span_begin(env, idx) != GW_OK) t_span_start = t_span_stop = nullptr;
+    if (prof_span_begin(env) != GW_OK) t_span_start = t_span_stop = nullptr;
 }
 
-}  // namespace
+// the launches in scope are one span of `kind` (timed = false: none); closed on every return
+// path, so no thread-local event outlives the scope.  Check `status` after opening.
+struct SpanGuard {
+    Env *env = nullptr;  // set while a span is open
+    int kind;
+    gw_status status = GW_OK;
+    SpanGuard(Env *e, bool timed, int k) : kind(k) {
+        if (timed && (status = prof_span_begin(e)) == GW_OK) env = e;
+    }
+    ~SpanGuard() {
+        if (env) prof_span_end(env, kind);
+    }
+    SpanGuard(const SpanGuard &) = delete;
+    SpanGuard &operator=(const SpanGuard &) = delete;
+};
 
-namespace gwprof {
-thread_local hipEvent_t t_span_start = nullptr, t_span_stop = nullptr, t_bind_stop = nullptr;
-
-bool span_begin(void *handle, size_t *idx) {
-    Env *env = static_cast<Env *>(handle);
-    if (!env || !env->profiling) return false;
-    return prof_span_begin(env, *idx) == GW_OK;
-}
-
-void span_end(void *handle, size_t idx, int kind) {
-    (void)prof_span_end(static_cast<Env *>(handle), idx, kind);
-}
-}  // namespace gwprof
-
-namespace {
+// the launches in scope carry the pipeline event `e` as their stop event (null: none)
+struct BindStop {
+    explicit BindStop(hipEvent_t e) { t_bind_stop = e; }
+    ~BindStop() { t_bind_stop = nullptr; }
+    BindStop(const BindStop &) = delete;
+    BindStop &operator=(const BindStop &) = delete;
+};
 
 template <typename T>
 gw_status dalloc(Env *env, T **ptr, size_t count) {
@@ -2387,6 +2318,11 @@ gw_status dalloc(Env *env, T **ptr, size_t count) {
     return GW_OK;
 }
 
+// ceil(2^32 / W): the kernels' division by W as a multiply
+uint32_t w_magic(int W) { return (uint32_t)((((uint64_t)1 << 32) + (uint64_t)W - 1) / (uint64_t)W); }
+
+// LDS bytes of the cell table (16-byte aligned: the Resp table follows it)
+int celltab_lds(int HW) { return ((HW * 4 + 15) / 16) * 16; }
 
 gw::Params make_params(const Env *env) {
     gw::Params p;
@@ -2403,13 +2339,13 @@ gw::Params make_params(const Env *env) {
     p.n_cdf = env->P * 2 * 9;
     p.lds_cdf = env->P <= 64 ? 1 : 0;
     p.ctab_off = p.lds_cdf ? ((p.n_cdf * 8 + 15) / 16) * 16 : 0;
-    p.resp_off = p.ctab_off + ((env->HW * 4 + 15) / 16) * 16;
+    p.resp_off = p.ctab_off + celltab_lds(env->HW);
     p.obs_be = env->obs_be;
     p.obs_bf16 = env->obs_bf16 ? 1 : 0;
     p.e_begin = 0;
     p.e_end = env->E;
     // the step kernels store records on the defer path; with inline FeAR only for an armed fear_alt
-    p.fwork = (env->mode == 3 && env->fear) || env->fear_alt ? env->fwork : nullptr;
+    p.fwork = defer_fear(env) || env->fear_alt ? env->fwork : nullptr;
     p.sims = env->sims;
     p.stats_row0 = 0;
     p.variant = env->variant;
@@ -2435,7 +2371,7 @@ gw::Params make_params(const Env *env) {
     p.auto_reset = env->auto_reset;
     p.key0 = (uint32_t)env->seed;
     p.key1 = (uint32_t)(env->seed >> 32);
-    p.w_magic = (uint32_t)((((uint64_t)1 << 32) + (uint64_t)env->W - 1) / (uint64_t)env->W);
+    p.w_magic = w_magic(env->W);
     {
         const uint64_t hw4 = (uint64_t)std::max(1, env->HW / 4);
         p.hw4_magic = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)1 << 32) + hw4 - 1) / hw4);
@@ -2446,54 +2382,298 @@ gw::Params make_params(const Env *env) {
     return p;
 }
 
-template <int N, int KMAX, bool FEAR, bool DEFER = false>
-hipError_t launch_v2(const Env *env, const gw::Params &p, hipStream_t s) {
-    constexpr int BE = gw::V2Cfg<N, KMAX, FEAR, false, DEFER>::BE;
-    const int64_t n = p.e_end - p.e_begin;  // this launch's env range (a pipeline chunk or all)
-    if (n <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((n + BE - 1) / BE);
-    // dynamic LDS [cdf][cell table][Resp (FeAR)].  (Staging the free-cell list there too for the
-    // auto-reset's spawn made C2's step kernel slower: 11.4 -> 12.2 us, profiles/r3_c2.)
-    const size_t dyn = (size_t)p.resp_off + (FEAR ? 100 * sizeof(double) : 0);
-    gw_launch((gw::step_v2<N, KMAX, FEAR, DEFER>), dim3(grid), dim3(gw::V2Cfg<N, KMAX, FEAR, false, DEFER>::THREADS),
-              dyn, s, p);
-    return hipGetLastError();
+// The kernels are templates of the agent count.  This is the only switch over it: f is a generic
+// lambda called with std::integral_constant<int, N>; `bad` is the result for an N outside 1..8.
+template <typename R, typename F>
+R with_agents(int n, R bad, F &&f) {
+    switch (n) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+    }
+    return bad;
 }
 
-// stats rows of the deferred world-update kernel; fear_v2's rows follow them
-template <int N>
-int64_t defer_step_rows(const Env *env) {
-    const int be = env->K <= 2 ? gw::V2Cfg<N, 2, false, false, true>::BE : gw::V2Cfg<N, N, false, false, true>::BE;
-    return (env->E + be - 1) / be;
+// the env's kernel variant: f(N, KMAX, WIDE) as integral constants.  KMAX = 2 for K <= 2, else N
+// (the width of the FeAR task lists); WIDE = the FeAR kernels' block width (fear_wide; the step
+// kernels have no such parameter and ignore it)
+template <typename R, typename F>
+R with_variant(const Env *env, R bad, F &&f) {
+    return with_agents(env->N, bad, [&](auto n) {
+        using Two = std::integral_constant<int, 2>;
+        if (env->fear_wide) return env->K <= 2 ? f(n, Two{}, std::true_type{}) : f(n, n, std::true_type{});
+        return env->K <= 2 ? f(n, Two{}, std::false_type{}) : f(n, n, std::false_type{});
+    });
 }
 
-template <int N, int KMAX, bool WIDE>
-hipError_t launch_fear_k(const Env *env, const gw::Params &p0, hipStream_t s) {
-    constexpr int BE = gw::V2Cfg<N, KMAX, true, WIDE>::BE;
-    gw::Params p = p0;
-    p.lds_cdf = 0;  // dynamic LDS [cell table][Resp]
+// Envs per block of the env's world-update kernel (.step: step_v2 or step_obs's step role) and of
+// its FeAR kernel (.fear: fear_v2 / fear_rows_kernel; 0 where FeAR runs inside the step kernel or
+// is off).  The one place that picks a V2Cfg<...>::BE for a path: the launch grids, the FeAR
+// kernels' stats_row0 and gw_stats_rows() all come from here, and so agree with the kernels' own
+// row index p.stats_row0 + e0 / BE.
+struct BlockEnvs { int step, fear; };
+
+BlockEnvs block_envs(const Env *env) {
+    return with_variant(env, BlockEnvs{0, 0}, [&](auto n, auto kmax, auto wide) {
+        constexpr int N = decltype(n)::value, KMAX = decltype(kmax)::value;
+        if (defer_fear(env))
+            return BlockEnvs{gw::V2Cfg<N, KMAX, false, false, true>::BE,
+                             gw::V2Cfg<N, KMAX, true, decltype(wide)::value>::BE};
+        return BlockEnvs{env->fear ? gw::V2Cfg<N, KMAX, true>::BE : gw::V2Cfg<N, KMAX, false>::BE, 0};
+    });
+}
+
+int64_t ceil_div(int64_t n, int64_t d) { return (n + d - 1) / d; }
+
+// dynamic LDS of the step kernels (step_v2, step_obs's step role): [cdf][cell table][Resp (FeAR)]
+// at make_params' offsets.  (Staging the free-cell list there too for the auto-reset's spawn made
+// C2's step kernel slower: 11.4 -> 12.2 us, profiles/r3_c2.)
+size_t step_lds(const gw::Params &p, bool fear) { return (size_t)p.resp_off + (fear ? 100 * sizeof(double) : 0); }
+
+// dynamic LDS of the FeAR kernels (fear_v2, fear_rows_kernel, fear_alt_kernel): [cell table][Resp].
+// Sets p's offsets for it and returns its size.
+size_t fear_lds(gw::Params &p) {
+    p.lds_cdf = 0;
     p.ctab_off = 0;
-    p.resp_off = ((env->HW * 4 + 15) / 16) * 16;
-    p.stats_row0 = defer_step_rows<N>(env);
+    p.resp_off = celltab_lds(p.HW);
+    return (size_t)p.resp_off + 100 * sizeof(double);
+}
+
+// the world-update kernel of the env's path over p's env range (a pipeline chunk or all)
+hipError_t launch_step(const Env *env, const gw::Params &p, hipStream_t s) {
+    const int64_t count = p.e_end - p.e_begin;
+    if (count <= 0) return hipSuccess;
+    return with_variant(env, hipErrorInvalidValue, [&](auto n, auto kmax, auto) {
+        constexpr int N = decltype(n)::value, KMAX = decltype(kmax)::value;
+        const dim3 grid((unsigned)ceil_div(count, block_envs(env).step)), block(gw::V2Cfg<N, KMAX, false>::THREADS);
+        if (defer_fear(env))  // the world update only, + FearRec
+            gw_launch((gw::step_v2<N, KMAX, false, true>), grid, block, step_lds(p, false), s, p);
+        else if (env->fear)  // FeAR inline (the merged path's step role, its synchronous steps)
+            gw_launch((gw::step_v2<N, KMAX, true>), grid, block, step_lds(p, true), s, p);
+        else
+            gw_launch((gw::step_v2<N, KMAX, false>), grid, block, step_lds(p, false), s, p);
+        return hipGetLastError();
+    });
+}
+
+// fear_v2 after a deferred world update; with `a`: fear_rows_kernel, the same FeAR blocks plus the
+// windows' row writer (a's P x P windows, whole env range) as the two block roles of one launch.
+// Their stats rows follow the world-update kernel's.
+hipError_t launch_fear(const Env *env, const gw::Params &p0, hipStream_t s, const gw::PatchArgs *a = nullptr) {
+    gw::Params p = p0;
+    const size_t dyn = fear_lds(p);
+    const int64_t count = p.e_end - p.e_begin;
+    if (!a && count <= 0) return hipSuccess;
+    return with_variant(env, hipErrorInvalidValue, [&](auto n, auto kmax, auto wide) {
+        constexpr int N = decltype(n)::value, KMAX = decltype(kmax)::value;
+        constexpr bool WIDE = decltype(wide)::value;
+        const BlockEnvs be = block_envs(env);
+        p.stats_row0 = ceil_div(env->E, be.step);
+        const unsigned nfear = (unsigned)ceil_div(count, be.fear);
+        if (a) {
+            const unsigned nrx = (unsigned)((a->E * a->P + 255) / 256);  // 2 waves x 2 runs x 64 rows per block
+            // one footprint for both roles: the FeAR tables or the row writer's 2 x 64 x 4 float4 slices
+            gw_launch((gw::fear_rows_kernel<N, KMAX, WIDE>), dim3(nfear + nrx * (unsigned)a->K), dim3(128),
+                      std::max(dyn, sizeof(float4) * 2 * 64 * 4), s, p, *a, nfear, nrx);
+        } else {
+            gw_launch((gw::fear_v2<N, KMAX, WIDE>), dim3(nfear), dim3(gw::V2Cfg<N, KMAX, true, WIDE>::THREADS), dyn,
+                      s, p);
+        }
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_fear_alt(const Env *env, const gw::Params &p0, hipStream_t s) {
+    gw::Params p = p0;
+    const size_t dyn = fear_lds(p);
+    const int64_t count = p.e_end - p.e_begin;
+    if (count <= 0) return hipSuccess;
+    return with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
+        gw_launch((gw::fear_alt_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(count, gw::ALT_WAVES)),
+                  dim3(gw::ALT_T), dyn, s, p, env->fear_alt);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
+    return with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
+        gw_launch((gw::reset_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(env->E, 256)), dim3(256), 0, s, p);
+        return hipGetLastError();
+    });
+}
+
+// gw_fear_matrix's kernel (N >= 2: the caller rejects N = 1, FeAR needs a second agent)
+hipError_t launch_fear_matrix(const Env *env, int64_t n_blocks, const gw::FmParams &q, hipStream_t s) {
+    return with_agents(env->N, hipErrorInvalidValue, [&](auto n) -> hipError_t {
+        constexpr int N = decltype(n)::value;
+        if constexpr (N >= 2) {
+            gw_launch((gw::fear_matrix_kernel<N>), dim3((unsigned)n_blocks), dim3(128), (size_t)celltab_lds(env->HW), s, q);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    });
+}
+
+// obs_kernel's LDS: road bitmask, OBS_BE flags, [2][obs_be][K][N + 1] patch cells + values
+// (+ with the f32 patch tables: [2][obs_be][K][N + 1] float4 entries and the byte tables)
+size_t obs_lds_bytes(const Env *env) {
+    const size_t base = sizeof(uint32_t) * ((env->HW + 31) / 32 + gw::OBS_BE) +
+                        (size_t)2 * 2 * env->obs_be * env->K * (env->N + 1) * sizeof(uint32_t);
+    if (env->obs_bf16 || !gw::obs_tab_ok(env->HW, env->obs_be, env->K)) return base;
+    return (size_t)gw::obs_ent_off(env->HW, env->obs_be, env->K, env->N + 1) +
+           (size_t)env->obs_be * env->K * (env->N + 1) * sizeof(float4) +
+           (size_t)gw::obs_tab_bytes(env->HW, env->obs_be, env->K);
+}
+
+// merged mode: step t (p) and the obs writer of step t-1 (q) as one step_obs launch
+hipError_t launch_step_obs(const Env *env, const gw::Params &p, const gw::Params &q, hipStream_t s) {
+    return with_variant(env, hipErrorInvalidValue, [&](auto n, auto kmax, auto) {
+        constexpr int N = decltype(n)::value, KMAX = decltype(kmax)::value;
+        const unsigned nstep = (unsigned)ceil_div(p.e_end - p.e_begin, block_envs(env).step);
+        const unsigned nobs = (unsigned)ceil_div(q.e_end - q.e_begin, env->obs_be);
+        const size_t dyn = std::max(step_lds(p, env->fear != 0), obs_lds_bytes(env));
+        if (env->fear)
+            gw_launch((gw::step_obs<N, KMAX, true>), dim3(nstep + nobs), dim3(128), dyn, s, p, q, q.out.obs,
+                      q.out.final_obs, nstep);
+        else
+            gw_launch((gw::step_obs<N, KMAX, false>), dim3(nstep + nobs), dim3(128), dyn, s, p, q, q.out.obs,
+                      q.out.final_obs, nstep);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_obs_range(const Env *env, const gw::Params &p, float *obs, float *final_obs, hipStream_t s) {
     const int64_t n = p.e_end - p.e_begin;
     if (n <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((n + BE - 1) / BE);
-    const size_t dyn = (size_t)p.resp_off + 100 * sizeof(double);
-    gw_launch((gw::fear_v2<N, KMAX, WIDE>), dim3(grid), dim3(gw::V2Cfg<N, KMAX, true, WIDE>::THREADS), dyn, s, p);
+    const unsigned grid = (unsigned)ceil_div(n, env->obs_be);
+    const size_t lds = obs_lds_bytes(env);
+    if (env->obs_bf16) {  // gw_set_obs_dtype checked HW % 8 == 0
+        gw_launch((gw::obs_kernel<true, true, true>), dim3(grid), dim3(gw::OBS_THREADS), lds, s, p, obs, final_obs);
+    } else if (env->HW % 4 == 0) {
+        gw_launch((gw::obs_kernel<true, true>), dim3(grid), dim3(gw::OBS_THREADS), lds, s, p, obs, final_obs);
+    } else {
+        gw_launch((gw::obs_kernel<false, false>), dim3(grid), dim3(gw::OBS_THREADS), lds, s, p, obs, final_obs);
+    }
     return hipGetLastError();
 }
 
-template <int N>
-hipError_t launch_fear(const Env *env, const gw::Params &p, hipStream_t s) {
-    if (env->fear_wide)
-        return env->K <= 2 ? launch_fear_k<N, 2, true>(env, p, s) : launch_fear_k<N, N, true>(env, p, s);
-    return env->K <= 2 ? launch_fear_k<N, 2, false>(env, p, s) : launch_fear_k<N, N, false>(env, p, s);
+// GW_OBS_CHUNKS = c > 1: the writer as c launches over consecutive env ranges.  The hardware
+// dispatches one kernel's workgroups ahead of a later kernel of another queue, so a single
+// long writer holds the CUs until its last workgroup is placed; between chunk launches the
+// caller stream's kernels (the next actor) get their turn.
+hipError_t launch_obs(Env *env, const gw::Params &p, float *obs, float *final_obs, hipStream_t s) {
+    if (!obs && !final_obs) return hipSuccess;
+    const int64_t n = p.e_end - p.e_begin;
+    if (n <= 0) return hipSuccess;
+    const int64_t blocks = ceil_div(n, env->obs_be);
+    const int64_t c = std::max<int64_t>(1, std::min<int64_t>(env->obs_chunks, blocks));
+    for (int64_t i = 0; i < c; ++i) {
+        if (i > 0) prof_span_split(env, GW_SPAN_OBS);  // profiled: one span per chunk
+        gw::Params q = p;
+        q.e_begin = p.e_begin + blocks * i / c * env->obs_be;
+        q.e_end = std::min(p.e_end, p.e_begin + blocks * (i + 1) / c * env->obs_be);
+        const hipError_t e = launch_obs_range(env, q, obs, final_obs, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
-template <int N>
-int fear_be(const Env *env) {
-    if (env->fear_wide) return env->K <= 2 ? gw::V2Cfg<N, 2, true, true>::BE : gw::V2Cfg<N, N, true, true>::BE;
-    return env->K <= 2 ? gw::V2Cfg<N, 2, true>::BE : gw::V2Cfg<N, N, true>::BE;
+// launch the queued obs_kernel on the obs stream, after its world update and (after != null)
+// after the caller's work up to `after`
+gw_status flush_obs(Env *env, hipEvent_t after, hipStream_t on = nullptr) {
+    if (!env->obs_queued) return GW_OK;
+    const gw::Params &q = env->qobs;
+    const bool prof = env->qobs_prof;  // timed iff the step that queued it was
+    if (env->mode == PATH_MERGED) {  // the last step's writer alone, on `on` (default: that step's stream)
+        SpanGuard span(env, prof, GW_SPAN_OBS);
+        GW_TRY(span.status);
+        HIP_TRY(launch_obs(env, q, q.out.obs, q.out.final_obs, on ? on : env->last_stream));
+        env->obs_queued = false;
+        return GW_OK;
+    }
+    // writers into the buffers of the last writer stay on its stream (write-after-write order);
+    // a writer into other buffers alternates to the other obs stream
+    const bool other = env->obs_streams > 1 && q.out.obs != env->obs_last[0] &&
+                       (q.out.final_obs == nullptr || q.out.final_obs != env->obs_last[1]);
+    if (other && !env->obs_stream2) HIP_TRY(hipStreamCreateWithFlags(&env->obs_stream2, hipStreamNonBlocking));
+    if (other) env->obs_cur ^= 1;
+    env->obs_last[0] = q.out.obs;
+    env->obs_last[1] = q.out.final_obs;
+    hipStream_t os = env->obs_cur ? env->obs_stream2 : env->obs_stream;
+    hipEvent_t done = env->obs_done[env->qobs_buf];
+    HIP_TRY(hipStreamWaitEvent(os, env->world_ev, 0));
+    if (after) HIP_TRY(hipStreamWaitEvent(os, after, 0));
+    {
+        SpanGuard span(env, prof, GW_SPAN_OBS);
+        GW_TRY(span.status);
+        BindStop bind(prof ? nullptr : done);  // untimed: obs_done carried by the writer's launch
+        HIP_TRY(launch_obs(env, q, q.out.obs, q.out.final_obs, os));
+    }
+    if (prof) HIP_TRY(hipEventRecord(done, os));
+    env->obs_pending[env->qobs_buf] = true;
+    env->obs_queued = false;
+    return GW_OK;
+}
+
+// make `s` wait for an async fear_v2 still in flight
+gw_status wait_fear(Env *env, hipStream_t s) {
+    if (env->fear_pending) HIP_TRY(hipStreamWaitEvent(s, env->fear_ev, 0));
+    return GW_OK;
+}
+
+// launch a queued obs_kernel and make `s` wait for every obs_kernel of the async-obs stream
+// (and for an async fear_v2: the callers rewrite state or descriptors in place)
+gw_status wait_obs(Env *env, hipStream_t s) {
+    GW_TRY(wait_fear(env, s));
+    if (env->obs_queued && env->mode == PATH_MERGED) {
+        // the writer runs on s, after the step that queued it (a graph replay of captured steps
+        // runs on s itself; its capture stream holds no work)
+        if (env->last_stream != s) {
+            GW_TRY(ensure_events(env, 1));
+            HIP_TRY(hipEventRecord(env->sync_ev[0], env->last_stream));
+            HIP_TRY(hipStreamWaitEvent(s, env->sync_ev[0], 0));
+        }
+        GW_TRY(flush_obs(env, nullptr, s));
+    } else {
+        GW_TRY(flush_obs(env, nullptr));
+    }
+    for (int i = 0; i < 2; ++i)
+        if (env->obs_pending[i]) HIP_TRY(hipStreamWaitEvent(s, env->obs_done[i], 0));
+    return GW_OK;
+}
+
+// launch a queued writer and wait on the host for it and for every writer in flight (the callers
+// change what a writer reads: the descriptor buffer in place, the obs format)
+gw_status drain_writers(Env *env) {
+    if (env->mode == PATH_MERGED) {  // the queued writer, on the last step's stream
+        if (!env->obs_queued) return GW_OK;
+        hipStream_t ls = env->last_stream;
+        GW_TRY(flush_obs(env, nullptr));
+        HIP_TRY(hipStreamSynchronize(ls));
+        return GW_OK;
+    }
+    if (!env->obs_stream) return GW_OK;  // never pipelined
+    GW_TRY(flush_obs(env, nullptr));
+    HIP_TRY(hipStreamSynchronize(env->obs_stream));
+    if (env->obs_stream2) HIP_TRY(hipStreamSynchronize(env->obs_stream2));
+    return GW_OK;
+}
+
+// the step that wrote descriptor buffer nb leaves its obs writer queued (launched by flush_obs:
+// at the next step, eagerly, or at a fence); nb becomes the current buffer
+void queue_writer(Env *env, const gw::Params &p, int nb) {
+    env->qobs = p;
+    env->qobs_buf = nb;
+    env->qobs_prof = env->profiling;
+    env->obs_queued = true;
+    env->dcur = nb;
+    env->desc = env->desc_buf[nb];
 }
 
 // the windows' writer args for the env's current descriptors (gw_obs_patch's, without its table)
@@ -2515,85 +2695,45 @@ gw::PatchArgs patch_args(const Env *env, int P, float *patch, float *final_patch
     return a;
 }
 
-template <int N, int KMAX, bool WIDE>
-hipError_t launch_fear_rows_k(const Env *env, const gw::Params &p0, const gw::PatchArgs &a, hipStream_t s) {
-    constexpr int BE = gw::V2Cfg<N, KMAX, true, WIDE>::BE;
-    gw::Params p = p0;
-    p.lds_cdf = 0;
-    p.ctab_off = 0;
-    p.resp_off = ((env->HW * 4 + 15) / 16) * 16;
-    p.stats_row0 = defer_step_rows<N>(env);
-    const int64_t n = p.e_end - p.e_begin;
-    const unsigned nfear = (unsigned)((n + BE - 1) / BE);
-    const unsigned nrx = (unsigned)((a.E * a.P + 255) / 256);  // 2 waves x 2 runs x 64 rows per block
-    // one footprint for both roles: the FeAR tables or the row writer's 2 x 64 x 4 float4 slices
-    const size_t dyn = std::max((size_t)p.resp_off + 100 * sizeof(double), sizeof(float4) * 2 * 64 * 4);
-    gw_launch((gw::fear_rows_kernel<N, KMAX, WIDE>), dim3(nfear + nrx * (unsigned)a.K), dim3(128), dyn, s, p, a,
-              nfear, nrx);
-    return hipGetLastError();
-}
-
-template <int N>
-hipError_t launch_fear_rows(const Env *env, const gw::Params &p, const gw::PatchArgs &a, hipStream_t s) {
-    if (env->fear_wide)
-        return env->K <= 2 ? launch_fear_rows_k<N, 2, true>(env, p, a, s) : launch_fear_rows_k<N, N, true>(env, p, a, s);
-    return env->K <= 2 ? launch_fear_rows_k<N, 2, false>(env, p, a, s) : launch_fear_rows_k<N, N, false>(env, p, a, s);
-}
-
-hipError_t dispatch_fear_rows(const Env *env, const gw::Params &p, const gw::PatchArgs &a, hipStream_t s) {
-    switch (env->N) {
-        case 1: return launch_fear_rows<1>(env, p, a, s);
-        case 2: return launch_fear_rows<2>(env, p, a, s);
-        case 3: return launch_fear_rows<3>(env, p, a, s);
-        case 4: return launch_fear_rows<4>(env, p, a, s);
-        case 5: return launch_fear_rows<5>(env, p, a, s);
-        case 6: return launch_fear_rows<6>(env, p, a, s);
-        case 7: return launch_fear_rows<7>(env, p, a, s);
-        case 8: return launch_fear_rows<8>(env, p, a, s);
+gw_status obs_patch_launch(Env *env, int32_t P, float *patch, float *final_patch, hipStream_t s) {
+    GW_TRY(wait_fear(env, s));  // async FeAR: the descriptors are written by the world update (joined)
+    gw::PatchArgs a = patch_args(env, P, patch, final_patch);
+    // the map part of each window (P <= 16) comes from a table of every centre's window (built on
+    // first use of this P; 0.5 MB at 32 x 32 and P = 11, 4 MB at 64 x 64 and P = 16);
+    const size_t tb = gw::window_table_bytes(env->H, env->W, P);
+    if (P * P <= 256 && tb <= (size_t)64 << 20) {
+        float *t = nullptr;
+        for (auto &pt : env->ptbls)
+            if (pt.first == P) t = pt.second;
+        if (!t) {
+            GW_TRY(dalloc(env, &t, tb / sizeof(float)));
+            HIP_TRY(gw::build_window_table(a, t, s));
+            // once per (env, P): later calls may come on other streams (a rollout's side stream)
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            HIP_TRY(hipStreamIsCapturing(s, &cs));
+            if (cs == hipStreamCaptureStatusNone) HIP_TRY(hipStreamSynchronize(s));
+            env->ptbls.emplace_back(P, t);
+        }
+        a.tbl = t;
     }
-    return hipErrorInvalidValue;
+    gwprof::Span span(env, GW_SPAN_WINDOW);
+    HIP_TRY(gw::launch_windows(a, s));
+    return GW_OK;
 }
 
-hipError_t dispatch_fear(const Env *env, const gw::Params &p, hipStream_t s) {
-    switch (env->N) {
-        case 1: return launch_fear<1>(env, p, s);
-        case 2: return launch_fear<2>(env, p, s);
-        case 3: return launch_fear<3>(env, p, s);
-        case 4: return launch_fear<4>(env, p, s);
-        case 5: return launch_fear<5>(env, p, s);
-        case 6: return launch_fear<6>(env, p, s);
-        case 7: return launch_fear<7>(env, p, s);
-        case 8: return launch_fear<8>(env, p, s);
+// ---- gw_step: the pieces its four paths share ----
+
+// the world update of p on s as a GW_SPAN_STEP span.  done != null: that event follows it,
+// carried by the launch itself, or recorded behind it when the span's timing events take that place
+gw_status world_update(Env *env, const gw::Params &p, hipStream_t s, hipEvent_t done = nullptr) {
+    {
+        SpanGuard span(env, env->profiling, GW_SPAN_STEP);
+        GW_TRY(span.status);
+        BindStop bind(env->profiling ? nullptr : done);
+        HIP_TRY(launch_step(env, p, s));
     }
-    return hipErrorInvalidValue;
-}
-
-template <int N>
-hipError_t launch_fear_alt(const Env *env, const gw::Params &p0, hipStream_t s) {
-    gw::Params p = p0;
-    p.lds_cdf = 0;  // dynamic LDS [cell table][Resp]
-    p.ctab_off = 0;
-    p.resp_off = ((env->HW * 4 + 15) / 16) * 16;
-    const int64_t n = p.e_end - p.e_begin;
-    if (n <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((n + gw::ALT_WAVES - 1) / gw::ALT_WAVES);
-    const size_t dyn = (size_t)p.resp_off + 100 * sizeof(double);
-    gw_launch((gw::fear_alt_kernel<N>), dim3(grid), dim3(gw::ALT_T), dyn, s, p, env->fear_alt);
-    return hipGetLastError();
-}
-
-hipError_t dispatch_fear_alt(const Env *env, const gw::Params &p, hipStream_t s) {
-    switch (env->N) {
-        case 1: return launch_fear_alt<1>(env, p, s);
-        case 2: return launch_fear_alt<2>(env, p, s);
-        case 3: return launch_fear_alt<3>(env, p, s);
-        case 4: return launch_fear_alt<4>(env, p, s);
-        case 5: return launch_fear_alt<5>(env, p, s);
-        case 6: return launch_fear_alt<6>(env, p, s);
-        case 7: return launch_fear_alt<7>(env, p, s);
-        case 8: return launch_fear_alt<8>(env, p, s);
-    }
-    return hipErrorInvalidValue;
+    if (done && env->profiling) HIP_TRY(hipEventRecord(done, s));
+    return GW_OK;
 }
 
 // gw_set_fear_alt: the step's per-action FeAR table, after the world update (which stored the
@@ -2604,165 +2744,158 @@ gw_status step_fear_alt(Env *env, const gw::Params &p, hipStream_t s) {
         HIP_TRY(hipMemsetAsync(env->fear_alt, 0, sizeof(double) * (size_t)env->E * env->K * GW_N_ACTIONS, s));
         return GW_OK;
     }
-    size_t b = 0;
-    if (env->profiling) GW_TRY(prof_span_begin(env, b));
-    HIP_TRY(dispatch_fear_alt(env, p, s));
-    if (env->profiling) GW_TRY(prof_span_end(env, b, GW_SPAN_FEAR_ALT));
+    SpanGuard span(env, env->profiling, GW_SPAN_FEAR_ALT);
+    GW_TRY(span.status);
+    HIP_TRY(launch_fear_alt(env, p, s));
     return GW_OK;
 }
 
-template <int N>
-hipError_t launch_step(const Env *env, const gw::Params &p, hipStream_t s) {
-    if (env->mode == 3 && env->fear)  // deferred FeAR: the world update only, + FearRec
-        return env->K <= 2 ? launch_v2<N, 2, false, true>(env, p, s) : launch_v2<N, N, false, true>(env, p, s);
-    if (env->fear)  // FeAR inline (the merged path's step role, its synchronous steps)
-        return env->K <= 2 ? launch_v2<N, 2, true>(env, p, s) : launch_v2<N, N, true>(env, p, s);
-    return env->K <= 2 ? launch_v2<N, 2, false>(env, p, s) : launch_v2<N, N, false>(env, p, s);
-}
-
-template <int N>
-hipError_t launch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
-    const unsigned grid = (unsigned)((env->E + 255) / 256);
-    gw_launch((gw::reset_kernel<N>), dim3(grid), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-hipError_t dispatch_step(const Env *env, const gw::Params &p, hipStream_t s) {
-    switch (env->N) {
-        case 1: return launch_step<1>(env, p, s);
-        case 2: return launch_step<2>(env, p, s);
-        case 3: return launch_step<3>(env, p, s);
-        case 4: return launch_step<4>(env, p, s);
-        case 5: return launch_step<5>(env, p, s);
-        case 6: return launch_step<6>(env, p, s);
-        case 7: return launch_step<7>(env, p, s);
-        case 8: return launch_step<8>(env, p, s);
+// the FeAR stage of a step on s, behind its world update: fear_v2 on the defer path (elsewhere FeAR
+// ran inside the step kernel: nothing to launch), then the fear_alt table.  A step without obs
+// outputs whose armed window request (gw_step_patch_next) meets the row writer's conditions over
+// the whole env range writes the windows in the same launch (fear_rows_kernel).
+gw_status fear_stage(Env *env, const gw::Params &p, hipStream_t s) {
+    if (defer_fear(env)) {
+        Env::PatchReq &rq = env->patch_req;
+        const int P = rq.P;
+        const bool rows = !p.out.obs && !p.out.final_obs && rq.armed && rq.patch && P >= 2 && P <= 16 &&
+                          env->E % 4 == 0 && env->N >= 1 && env->N <= 8 &&
+                          (uint64_t)env->E * (uint64_t)P < (1ull << 32) && p.e_begin == 0 && p.e_end == env->E;
+        SpanGuard span(env, env->profiling, GW_SPAN_FEAR);
+        GW_TRY(span.status);
+        if (rows) {
+            gw::PatchArgs a = patch_args(env, P, rq.patch, rq.final_patch);
+            a.desc = p.desc;  // the buffer the world update just wrote
+            HIP_TRY(launch_fear(env, p, s, &a));
+            rq.done = true;
+        } else {
+            HIP_TRY(launch_fear(env, p, s));
+        }
     }
-    return hipErrorInvalidValue;
+    return step_fear_alt(env, p, s);
 }
 
-hipError_t dispatch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
-    switch (env->N) {
-        case 1: return launch_reset<1>(env, p, s);
-        case 2: return launch_reset<2>(env, p, s);
-        case 3: return launch_reset<3>(env, p, s);
-        case 4: return launch_reset<4>(env, p, s);
-        case 5: return launch_reset<5>(env, p, s);
-        case 6: return launch_reset<6>(env, p, s);
-        case 7: return launch_reset<7>(env, p, s);
-        case 8: return launch_reset<8>(env, p, s);
-    }
-    return hipErrorInvalidValue;
+// the step's obs writer on s as a GW_SPAN_OBS span (one per chunk)
+gw_status write_obs(Env *env, const gw::Params &p, hipStream_t s) {
+    SpanGuard span(env, env->profiling, GW_SPAN_OBS);
+    GW_TRY(span.status);
+    HIP_TRY(launch_obs(env, p, p.out.obs, p.out.final_obs, s));
+    return GW_OK;
 }
 
-hipError_t launch_obs_range(const Env *env, const gw::Params &p, float *obs, float *final_obs, hipStream_t s);
+// ---- gw_step: the four paths ----
 
-// obs_kernel's LDS: road bitmask, OBS_BE flags, [2][obs_be][K][N + 1] patch cells + values
-// (+ with the f32 patch tables: [2][obs_be][K][N + 1] float4 entries and the byte tables)
-size_t obs_lds_bytes(const Env *env) {
-    const size_t base = sizeof(uint32_t) * ((env->HW + 31) / 32 + gw::OBS_BE) +
-                        (size_t)2 * 2 * env->obs_be * env->K * (env->N + 1) * sizeof(uint32_t);
-    if (env->obs_bf16 || !gw::obs_tab_ok(env->HW, env->obs_be, env->K)) return base;
-    return (size_t)gw::obs_ent_off(env->HW, env->obs_be, env->K, env->N + 1) +
-           (size_t)env->obs_be * env->K * (env->N + 1) * sizeof(float4) +
-           (size_t)gw::obs_tab_bytes(env->HW, env->obs_be, env->K);
-}
-
-template <int N, int KMAX, bool FEAR>
-hipError_t launch_step_obs_k(const Env *env, const gw::Params &p, const gw::Params &q, hipStream_t s) {
-    constexpr int BE = gw::V2Cfg<N, KMAX, FEAR>::BE;
-    const int64_t n = p.e_end - p.e_begin, nq = q.e_end - q.e_begin;
-    const unsigned nstep = (unsigned)((n + BE - 1) / BE);
-    const unsigned nobs = (unsigned)((nq + env->obs_be - 1) / env->obs_be);
-    const size_t step_dyn = (size_t)p.resp_off + (FEAR ? 100 * sizeof(double) : 0);
-    const size_t dyn = std::max(step_dyn, obs_lds_bytes(env));
-    gw_launch((gw::step_obs<N, KMAX, FEAR>), dim3(nstep + nobs), dim3(128), dyn, s, p, q, q.out.obs, q.out.final_obs,
-              nstep);
-    return hipGetLastError();
-}
-
-template <int N>
-hipError_t launch_step_obs_n(const Env *env, const gw::Params &p, const gw::Params &q, hipStream_t s) {
-    if (env->fear)
-        return env->K <= 2 ? launch_step_obs_k<N, 2, true>(env, p, q, s) : launch_step_obs_k<N, N, true>(env, p, q, s);
-    return env->K <= 2 ? launch_step_obs_k<N, 2, false>(env, p, q, s) : launch_step_obs_k<N, N, false>(env, p, q, s);
-}
-
-// merged mode: step t (p) and the obs writer of step t-1 (q) as one step_obs launch
-hipError_t launch_step_obs(const Env *env, const gw::Params &p, const gw::Params &q, hipStream_t s) {
-    switch (env->N) {
-        case 1: return launch_step_obs_n<1>(env, p, q, s);
-        case 2: return launch_step_obs_n<2>(env, p, q, s);
-        case 3: return launch_step_obs_n<3>(env, p, q, s);
-        case 4: return launch_step_obs_n<4>(env, p, q, s);
-        case 5: return launch_step_obs_n<5>(env, p, q, s);
-        case 6: return launch_step_obs_n<6>(env, p, q, s);
-        case 7: return launch_step_obs_n<7>(env, p, q, s);
-        case 8: return launch_step_obs_n<8>(env, p, q, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// GW_OBS_CHUNKS = c > 1: the writer as c launches over consecutive env ranges.  The hardware
-// dispatches one kernel's workgroups ahead of a later kernel of another queue, so a single
-// long writer holds the CUs until its last workgroup is placed; between chunk launches the
-// caller stream's kernels (the next actor) get their turn.
-hipError_t launch_obs(const Env *env, const gw::Params &p, float *obs, float *final_obs, hipStream_t s) {
-    if (!obs && !final_obs) return hipSuccess;
-    const int64_t n = p.e_end - p.e_begin;
-    if (n <= 0) return hipSuccess;
-    const int64_t blocks = (n + env->obs_be - 1) / env->obs_be;
-    const int64_t c = std::max<int64_t>(1, std::min<int64_t>(env->obs_chunks, blocks));
-    for (int64_t i = 0; i < c; ++i) {
-        if (i > 0) prof_span_split(const_cast<Env *>(env), 1);  // profiled: one span per chunk
-        gw::Params q = p;
-        q.e_begin = p.e_begin + blocks * i / c * env->obs_be;
-        q.e_end = std::min(p.e_end, p.e_begin + blocks * (i + 1) / c * env->obs_be);
-        const hipError_t e = launch_obs_range(env, q, obs, final_obs, s);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t launch_obs_range(const Env *env, const gw::Params &p, float *obs, float *final_obs, hipStream_t s) {
-    const int64_t n = p.e_end - p.e_begin;
-    if (n <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((n + env->obs_be - 1) / env->obs_be);
-    const size_t lds = obs_lds_bytes(env);
-    if (env->obs_bf16) {  // gw_set_obs_dtype checked HW % 8 == 0
-        gw_launch((gw::obs_kernel<true, true, true>), dim3(grid), dim3(gw::OBS_THREADS), lds, s, p, obs, final_obs);
-    } else if (env->HW % 4 == 0) {
-        gw_launch((gw::obs_kernel<true, true>), dim3(grid), dim3(gw::OBS_THREADS), lds, s, p, obs, final_obs);
+// Merged pipeline: ONE launch per step on the caller's stream: this step's world update
+// + FeAR (writing descriptor buffer nb) and the obs writer of the previous step (reading
+// the other buffer) as the two block roles of step_obs (§5.7).  The writer of the last
+// step stays queued until the next step or a fence.
+gw_status step_merged_async(Env *env, gw::Params &p, hipStream_t s) {
+    env->last_stream = s;
+    const int nb = env->dcur ^ 1;
+    p.desc = env->desc_buf[nb];
+    if (env->obs_queued) {
+        SpanGuard span(env, env->profiling, GW_SPAN_OBS);
+        GW_TRY(span.status);
+        HIP_TRY(launch_step_obs(env, p, env->qobs, s));
     } else {
-        gw_launch((gw::obs_kernel<false, false>), dim3(grid), dim3(gw::OBS_THREADS), lds, s, p, obs, final_obs);
+        GW_TRY(world_update(env, p, s));
     }
-    return hipGetLastError();
+    GW_TRY(fear_stage(env, p, s));
+    queue_writer(env, p, nb);
+    return GW_OK;
 }
 
-}  // namespace
-
-namespace {
-template <int N>
-int64_t stats_rows_n(const Env *env) {
-    int be;
-    if (env->mode == 3 && env->fear) {
-        const int bf = fear_be<N>(env);
-        return defer_step_rows<N>(env) + (env->E + bf - 1) / bf;
+// Software pipeline over steps.  The world update (and FeAR) of step t runs on s
+// (rewards, dones, masks, state, stats: stream-ordered as usual).  The obs writer of
+// step t runs on obs_stream right after the world update (eager), or is queued and
+// launched at the start of step t+1 behind the caller's work in between (lazy), and
+// overlaps FeAR and the world update + FeAR of step t+1, which read only the state.
+// The descriptor is double-buffered: step t writes desc_buf[nb]; obs_kernel(t-2) read
+// that buffer, so the world update waits for it.
+gw_status step_defer_async(Env *env, gw::Params &p, hipStream_t s) {
+    GW_TRY(ensure_obs_stream(env));
+    // the world update + FeAR chain runs on the caller's stream itself (no fork / join hops
+    // between consecutive steps); only with the unjoined FeAR (| 4) does it go to the aux stream
+    const bool on_aux = defer_fear(env) && env->fear_async;
+    if (on_aux) GW_TRY(ensure_aux(env, 3));
+    hipStream_t ws = on_aux ? env->aux : s;
+    if (on_aux || env->obs_queued) HIP_TRY(hipEventRecord(env->sync_ev[0], s));  // the caller's prior work
+    GW_TRY(flush_obs(env, env->sync_ev[0]));       // lazy: obs_kernel(t-1), behind that work
+    const int nb = env->dcur ^ 1;
+    p.desc = env->desc_buf[nb];
+    if (on_aux) HIP_TRY(hipStreamWaitEvent(ws, env->sync_ev[0], 0));
+    if (env->obs_pending[nb]) HIP_TRY(hipStreamWaitEvent(ws, env->obs_done[nb], 0));
+    GW_TRY(world_update(env, p, ws, env->world_ev));
+    // unjoined FeAR: s joins the world update only: the caller's next work (the actor reads the
+    // descriptors and masks) overlaps fear_v2; the FeAR-owned outputs (fear_alt among them) wait
+    // for gw_fear_fence
+    if (on_aux) HIP_TRY(hipStreamWaitEvent(s, env->world_ev, 0));
+    GW_TRY(fear_stage(env, p, ws));
+    if (on_aux) {
+        HIP_TRY(hipEventRecord(env->fear_ev, ws));
+        env->fear_pending = true;
     }
-    if (env->fear) be = env->K <= 2 ? gw::V2Cfg<N, 2, true>::BE : gw::V2Cfg<N, N, true>::BE;
-    else be = env->K <= 2 ? gw::V2Cfg<N, 2, false>::BE : gw::V2Cfg<N, N, false>::BE;
-    return (env->E + be - 1) / be;
+    queue_writer(env, p, nb);
+    if (!env->obs_lazy) GW_TRY(flush_obs(env, nullptr));  // eager: right after the world update
+    return GW_OK;
 }
+
+// defer, synchronous obs: world update; then fear_v2 on the aux stream || obs_kernel on s; join
+gw_status step_defer_sync(Env *env, const gw::Params &p, hipStream_t s) {
+    GW_TRY(world_update(env, p, s));
+    if (!p.out.obs && !p.out.final_obs) return fear_stage(env, p, s);  // no writer to run beside
+    GW_TRY(ensure_aux(env, 2));
+    HIP_TRY(hipEventRecord(env->sync_ev[0], s));  // fork after the world update
+    HIP_TRY(hipStreamWaitEvent(env->aux, env->sync_ev[0], 0));
+    GW_TRY(fear_stage(env, p, env->aux));  // fear_alt too: beside the writer, as fear_v2
+    GW_TRY(write_obs(env, p, s));
+    HIP_TRY(hipEventRecord(env->sync_ev[1], env->aux));
+    HIP_TRY(hipStreamWaitEvent(s, env->sync_ev[1], 0));
+    return GW_OK;
+}
+
+// plain: the step kernel (FeAR inline or off), then the writer, on s
+gw_status step_plain(Env *env, const gw::Params &p, hipStream_t s) {
+    GW_TRY(world_update(env, p, s));
+    GW_TRY(fear_stage(env, p, s));
+    if (p.out.obs || p.out.final_obs) GW_TRY(write_obs(env, p, s));
+    return GW_OK;
+}
+
+gw_status step_body(Env *env, const int32_t *rl_actions, const int32_t *scripted, const int32_t *spawn,
+                    const gw_step_out *out, hipStream_t s) {
+    if (!env->initialized) return fail(GW_ERR_STATE, "gw_step before gw_reset");
+    gw::Params p = make_params(env);
+    p.rl = rl_actions;
+    p.scripted = scripted;
+    p.spawn = spawn;
+    if (out) p.out = *out;
+    if (env->profiling) env->steps_timed++;
+    if (env->obs_async && (p.out.obs || p.out.final_obs))
+        return env->mode == PATH_MERGED ? step_merged_async(env, p, s) : step_defer_async(env, p, s);
+    // every other path writes the current descriptor buffer in place: an async obs_kernel still
+    // reading it (a step without obs outputs, or a non-pipelining kernel path) must finish first
+    if (env->obs_async || env->fear_pending) GW_TRY(wait_obs(env, s));
+    return defer_fear(env) ? step_defer_sync(env, p, s) : step_plain(env, p, s);
+}
+
+// gw_pipeline_save / gw_pipeline_load: the host-side state a merged-path step leaves behind
+struct PipeState {
+    gw::Params qobs;
+    int32_t qobs_buf, dcur, obs_queued, mode;
+    uint32_t *desc;
+};
+
 }  // namespace
 
-namespace {
-template <int N>
-hipError_t launch_fear_matrix(const Env *env, int64_t n, const gw::FmParams &q, hipStream_t s) {
-    const size_t dyn = ((size_t)env->HW * 4 + 15) / 16 * 16;
-    gw_launch((gw::fear_matrix_kernel<N>), dim3((unsigned)n), dim3(128), dyn, s, q);
-    return hipGetLastError();
+thread_local hipEvent_t gwprof::t_span_start = nullptr, gwprof::t_span_stop = nullptr, gwprof::t_bind_stop = nullptr;
+
+bool gwprof::span_begin(void *handle) {
+    Env *env = static_cast<Env *>(handle);
+    return env && env->profiling && prof_span_begin(env) == GW_OK;
 }
-}  // namespace
+
+void gwprof::span_end(void *handle, int kind) { prof_span_end(static_cast<Env *>(handle), kind); }
 
 extern "C" {
 
@@ -2855,14 +2988,14 @@ gw_status gw_create(const gw_scenario *sc, const gw_config *cfg, int device, voi
         // GW_KERNEL=defer|merged forces one of the two (result-neutral: both are pinned to the
         // oracle by tests/test_gpu_parity.py)
         const char *kv = std::getenv("GW_KERNEL");
-        env->mode = 3;
+        env->mode = PATH_DEFER;
         if (HW % 4 == 0) {
             const char *mb = std::getenv("GW_MERGE_BYTES");
             const int64_t lim = mb ? std::atoll(mb) : ((int64_t)160 << 20);
-            if (cfg->num_envs * (int64_t)K * HW * 4 <= lim) env->mode = 4;
-            if (kv && std::strcmp(kv, "merged") == 0) env->mode = 4;
+            if (cfg->num_envs * (int64_t)K * HW * 4 <= lim) env->mode = PATH_MERGED;
+            if (kv && std::strcmp(kv, "merged") == 0) env->mode = PATH_MERGED;
         }
-        if (kv && std::strcmp(kv, "defer") == 0) env->mode = 3;
+        if (kv && std::strcmp(kv, "defer") == 0) env->mode = PATH_DEFER;
         // fear_v2 block size (result-neutral): wide (default) or narrow (the bf16 obs default)
         const char *fb = std::getenv("GW_FEAR_BE");
         if (fb && std::strcmp(fb, "wide") == 0) env->fear_wide = true;
@@ -2872,7 +3005,7 @@ gw_status gw_create(const gw_scenario *sc, const gw_config *cfg, int device, voi
         // runs alone (32x32 K=2 -> 2 envs, 64x64 -> 1), 8 while fear_v2 shares the CUs (32x32 ->
         // 4 envs: 2.5 % faster step at C3)
         int be_def = std::max(1, 4096 / std::max(1, K * HW));
-        if (env->mode == 3 && env->fear) be_def *= 2;
+        if (defer_fear(env)) be_def *= 2;
         env->obs_be = std::max(1, std::min(8, be_def));  // f32 default <= 8 envs per block
         env->obs_be_f32 = env->obs_be;
         // scheduling of the async writer (result-neutral): c launches per step, one or two streams
@@ -2899,7 +3032,7 @@ gw_status gw_create(const gw_scenario *sc, const gw_config *cfg, int device, voi
         (st = dalloc(env, &env->episode, E)) || (st = dalloc(env, &env->desc, 2 * E * gw::NDESC)) ||
         (st = dalloc(env, &env->score, E)) || (st = dalloc(env, &env->fscore, E)) ||
         (st = dalloc(env, &env->celltab, HW)) || (st = dalloc(env, &env->roadbits, rbits.size())) ||
-        (env->mode == 3 && env->fear && (st = dalloc(env, &env->fwork, E * (N <= 4 ? 1 : 2)))))
+        (defer_fear(env) && (st = dalloc(env, &env->fwork, E * (N <= 4 ? 1 : 2)))))
         return cleanup(st);
     hipError_t he = hipSuccess;
 #define CP(dst, src, n) if (he == hipSuccess) he = hipMemcpy(dst, src, n, hipMemcpyHostToDevice)
@@ -2935,22 +3068,17 @@ gw_status gw_reset(void *handle, const uint8_t *env_mask, const int32_t *spawn_c
     p.out.mask = mask;
     hipStream_t s = static_cast<hipStream_t>(stream);
     GW_TRY(wait_obs(env, s));  // async obs: the descriptors are rewritten in place below
-    HIP_TRY(dispatch_reset(env, p, s));
+    HIP_TRY(launch_reset(env, p, s));
     HIP_TRY(launch_obs(env, p, obs, nullptr, s));
     env->initialized = true;
     return GW_OK;
 }
 
-static gw_status obs_patch_launch(Env *env, int32_t P, float *patch, float *final_patch, hipStream_t s);
-
-static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int32_t *scripted,
-                              const int32_t *spawn, const gw_step_out *out, void *stream);
-
 gw_status gw_step(void *handle, const int32_t *rl_actions, const int32_t *scripted,
                   const int32_t *spawn, const gw_step_out *out, void *stream) {
     Env *env = static_cast<Env *>(handle);
     if (!env) return fail(GW_ERR_ARG, "null env");
-    const gw_status st = gw_step_body(handle, rl_actions, scripted, spawn, out, stream);
+    const gw_status st = step_body(env, rl_actions, scripted, spawn, out, static_cast<hipStream_t>(stream));
     Env::PatchReq rq = env->patch_req;
     env->patch_req = Env::PatchReq{};
     if (st != GW_OK || !rq.armed || rq.done) return st;
@@ -2971,182 +3099,12 @@ gw_status gw_step_patch_next(void *handle, int32_t P, float *patch, float *final
     return GW_OK;
 }
 
-static gw_status gw_step_body(void *handle, const int32_t *rl_actions, const int32_t *scripted,
-                              const int32_t *spawn, const gw_step_out *out, void *stream) {
-    Env *env = static_cast<Env *>(handle);
-    if (!env) return fail(GW_ERR_ARG, "null env");
-    if (!env->initialized) return fail(GW_ERR_STATE, "gw_step before gw_reset");
-    gw::Params p = make_params(env);
-    p.rl = rl_actions;
-    p.scripted = scripted;
-    p.spawn = spawn;
-    if (out) p.out = *out;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool want_obs = p.out.obs || p.out.final_obs;
-    if (env->profiling) env->steps_timed++;
-    auto span_begin = [&](hipStream_t, size_t &idx) -> gw_status {
-        idx = 0;
-        return env->profiling ? prof_span_begin(env, idx) : GW_OK;
-    };
-    auto span_end = [&](hipStream_t, size_t b, int kind) -> gw_status {
-        return env->profiling ? prof_span_end(env, b, kind) : GW_OK;
-    };
-    const bool defer = env->mode == 3 && env->fear;
-    if (env->obs_async && want_obs && env->mode == 4) {
-        // Merged pipeline: ONE launch per step on the caller's stream: this step's world update
-        // + FeAR (writing descriptor buffer nb) and the obs writer of the previous step (reading
-        // the other buffer) as the two block roles of step_obs (§5.7).  The writer of the last
-        // step stays queued until the next step or a fence.
-        env->last_stream = s;
-        const int nb = env->dcur ^ 1;
-        p.desc = env->desc_buf[nb];
-        const bool merge = env->obs_queued;
-        size_t b;
-        GW_TRY(span_begin(s, b));
-        if (merge)
-            HIP_TRY(launch_step_obs(env, p, env->qobs, s));
-        else
-            HIP_TRY(dispatch_step(env, p, s));
-        GW_TRY(span_end(s, b, merge ? 1 : 0));
-        GW_TRY(step_fear_alt(env, p, s));
-        env->qobs = p;
-        env->qobs_buf = nb;
-        env->qobs_prof = env->profiling;
-        env->obs_queued = true;
-        env->dcur = nb;
-        env->desc = env->desc_buf[nb];
-        return GW_OK;
-    }
-    if (env->obs_async && want_obs && env->mode == 3) {
-        // Software pipeline over steps.  The world update (and FeAR) of step t runs on s
-        // (rewards, dones, masks, state, stats: stream-ordered as usual).  The obs writer of
-        // step t runs on obs_stream right after the world update (eager), or is queued and
-        // launched at the start of step t+1 behind the caller's work in between (lazy), and
-        // overlaps FeAR and the world update + FeAR of step t+1, which read only the state.
-        // The descriptor is double-buffered: step t writes desc_buf[nb]; obs_kernel(t-2) read
-        // that buffer, so the world update waits for it.
-        GW_TRY(ensure_obs_stream(env));
-        // the world update + FeAR chain runs on the caller's stream itself (no fork / join hops
-        // between consecutive steps); only with the unjoined FeAR (| 4) does it go to the aux stream
-        const bool on_aux = defer && env->fear_async;
-        if (on_aux) GW_TRY(ensure_aux(env, 3));
-        hipStream_t ws = on_aux ? env->aux : s;
-        if (on_aux || env->obs_queued) HIP_TRY(hipEventRecord(env->sync_ev[0], s));  // the caller's prior work
-        GW_TRY(flush_obs(env, env->sync_ev[0]));       // lazy: obs_kernel(t-1), behind that work
-        const int nb = env->dcur ^ 1;
-        p.desc = env->desc_buf[nb];
-        size_t b;
-        if (on_aux) HIP_TRY(hipStreamWaitEvent(ws, env->sync_ev[0], 0));
-        if (env->obs_pending[nb]) HIP_TRY(hipStreamWaitEvent(ws, env->obs_done[nb], 0));
-        GW_TRY(span_begin(ws, b));
-        const bool bind = !env->profiling;  // world_ev carried by the launch
-        if (bind) t_bind_stop = env->world_ev;
-        const hipError_t se = dispatch_step(env, p, ws);
-        t_bind_stop = nullptr;
-        HIP_TRY(se);
-        GW_TRY(span_end(ws, b, 0));
-        if (!bind) HIP_TRY(hipEventRecord(env->world_ev, ws));
-        if (defer && env->fear_async) {
-            // s joins the world update only: the caller's next work (the actor reads the
-            // descriptors and masks) overlaps fear_v2; FeAR-owned outputs wait for gw_fear_fence
-            HIP_TRY(hipStreamWaitEvent(s, env->world_ev, 0));
-            GW_TRY(span_begin(ws, b));
-            HIP_TRY(dispatch_fear(env, p, ws));
-            GW_TRY(span_end(ws, b, 2));
-            GW_TRY(step_fear_alt(env, p, ws));  // a FeAR-owned output: behind gw_fear_fence
-            HIP_TRY(hipEventRecord(env->fear_ev, ws));
-            env->fear_pending = true;
-        } else {
-            if (defer) {
-                GW_TRY(span_begin(ws, b));
-                HIP_TRY(dispatch_fear(env, p, ws));
-                GW_TRY(span_end(ws, b, 2));
-            }
-            GW_TRY(step_fear_alt(env, p, ws));
-            if (on_aux) {
-                HIP_TRY(hipEventRecord(env->sync_ev[2], ws));  // join the world update + FeAR
-                HIP_TRY(hipStreamWaitEvent(s, env->sync_ev[2], 0));
-            }
-        }
-        env->qobs = p;
-        env->qobs_buf = nb;
-        env->qobs_prof = env->profiling;
-        env->obs_queued = true;
-        if (!env->obs_lazy) GW_TRY(flush_obs(env, nullptr));  // eager: right after the world update
-        env->dcur = nb;
-        env->desc = env->desc_buf[nb];
-        return GW_OK;
-    }
-    // every other path writes the current descriptor buffer in place: an async obs_kernel still
-    // reading it (a step without obs outputs, or a non-pipelining kernel path) must finish first
-    if (env->obs_async || env->fear_pending) GW_TRY(wait_obs(env, s));
-    if (defer) {
-        // world update; then fear_v2 on the aux stream || obs_kernel on s; join
-        size_t b;
-        GW_TRY(span_begin(s, b));
-        HIP_TRY(dispatch_step(env, p, s));
-        GW_TRY(span_end(s, b, 0));
-        if (!want_obs) {
-            Env::PatchReq &rq = env->patch_req;
-            const int P = rq.P;
-            // the requested windows inside the FeAR launch: the row writer's conditions, whole range
-            const bool rows = rq.armed && rq.patch && P >= 2 && P <= 16 && env->E % 4 == 0 &&
-                              env->N >= 1 && env->N <= 8 && (uint64_t)env->E * (uint64_t)P < (1ull << 32) &&
-                              p.e_begin == 0 && p.e_end == env->E;
-            GW_TRY(span_begin(s, b));
-            if (rows) {
-                // (the world update just wrote env->desc: p.desc is that buffer)
-                gw::PatchArgs a = patch_args(env, P, rq.patch, rq.final_patch);
-                a.desc = p.desc;
-                HIP_TRY(dispatch_fear_rows(env, p, a, s));
-                rq.done = true;
-            } else {
-                HIP_TRY(dispatch_fear(env, p, s));
-            }
-            GW_TRY(span_end(s, b, 2));
-            GW_TRY(step_fear_alt(env, p, s));
-            return GW_OK;
-        }
-        GW_TRY(ensure_aux(env, 2));
-        HIP_TRY(hipEventRecord(env->sync_ev[0], s));  // fork after the world update
-        HIP_TRY(hipStreamWaitEvent(env->aux, env->sync_ev[0], 0));
-        GW_TRY(span_begin(env->aux, b));
-        HIP_TRY(dispatch_fear(env, p, env->aux));
-        GW_TRY(span_end(env->aux, b, 2));
-        GW_TRY(step_fear_alt(env, p, env->aux));  // beside the writer, as fear_v2
-        GW_TRY(span_begin(s, b));
-        HIP_TRY(launch_obs(env, p, p.out.obs, p.out.final_obs, s));
-        GW_TRY(span_end(s, b, 1));
-        HIP_TRY(hipEventRecord(env->sync_ev[1], env->aux));
-        HIP_TRY(hipStreamWaitEvent(s, env->sync_ev[1], 0));
-        return GW_OK;
-    }
-    size_t b;
-    GW_TRY(span_begin(s, b));
-    HIP_TRY(dispatch_step(env, p, s));
-    GW_TRY(span_end(s, b, 0));
-    GW_TRY(step_fear_alt(env, p, s));
-    if (want_obs) {
-        GW_TRY(span_begin(s, b));
-        HIP_TRY(launch_obs(env, p, p.out.obs, p.out.final_obs, s));
-        GW_TRY(span_end(s, b, 1));
-    }
-    return GW_OK;
-}
-
 gw_status gw_set_obs_async(void *handle, int enable) {
     Env *env = static_cast<Env *>(handle);
     if (!env) return fail(GW_ERR_ARG, "null env");
-    if (!enable && env->obs_async && env->mode == 4 && env->obs_queued) {  // merged: drain the queued writer
-        hipStream_t ls = env->last_stream;
-        GW_TRY(flush_obs(env, nullptr));
-        HIP_TRY(hipStreamSynchronize(ls));
-    }
-    if (!enable && env->obs_async && env->obs_stream) {
-        // the synchronous path writes the current descriptor buffer in place: drain the writer
-        GW_TRY(flush_obs(env, nullptr));
-        HIP_TRY(hipStreamSynchronize(env->obs_stream));
-        if (env->obs_stream2) HIP_TRY(hipStreamSynchronize(env->obs_stream2));
+    if (!enable && env->obs_async) {
+        // the synchronous path writes the current descriptor buffer in place: no writer may still read it
+        GW_TRY(drain_writers(env));
         env->obs_pending[0] = env->obs_pending[1] = false;
     }
     if (!(enable & 4) && env->fear_pending) {
@@ -3173,17 +3131,8 @@ gw_status gw_set_obs_dtype(void *handle, int dtype) {
     if (dtype == GW_OBS_BF16 && env->HW % 8 != 0)
         return fail(GW_ERR_ARG, "gw_set_obs_dtype: bf16 obs needs H*W % 8 == 0");
     const bool bf = dtype == GW_OBS_BF16;
-    if (bf != env->obs_bf16 && env->mode == 4 && env->obs_queued) {  // merged: the queued writer
-        hipStream_t ls = env->last_stream;
-        GW_TRY(flush_obs(env, nullptr));
-        HIP_TRY(hipStreamSynchronize(ls));
-    }
-    if (bf != env->obs_bf16 && env->obs_stream) {
-        // an obs_kernel still queued or in flight was sized for the old format: drain it first
-        GW_TRY(flush_obs(env, nullptr));
-        HIP_TRY(hipStreamSynchronize(env->obs_stream));
-        if (env->obs_stream2) HIP_TRY(hipStreamSynchronize(env->obs_stream2));
-    }
+    // an obs_kernel still queued or in flight was sized for the old format: drain it first
+    if (bf != env->obs_bf16) GW_TRY(drain_writers(env));
     // bf16 writer: ~64 KB of obs per block (C3: 16 envs, 4.3 TB/s; 4 envs 3.4, 8 envs 4.2;
     // C4: 4 envs; profiles/r1_bf16); f32: the create-time default
     env->obs_be = bf ? std::max(1, std::min(gw::OBS_BE, 32768 / std::max(1, env->K * env->HW)))
@@ -3308,21 +3257,12 @@ gw_status gw_copy_state(void *handle, const gw_state *buf, int to_env, void *str
     return GW_OK;
 }
 
-
 int64_t gw_stats_rows(void *handle) {
     const Env *env = static_cast<const Env *>(handle);
     if (!env) return -1;
-    switch (env->N) {
-        case 1: return stats_rows_n<1>(env);
-        case 2: return stats_rows_n<2>(env);
-        case 3: return stats_rows_n<3>(env);
-        case 4: return stats_rows_n<4>(env);
-        case 5: return stats_rows_n<5>(env);
-        case 6: return stats_rows_n<6>(env);
-        case 7: return stats_rows_n<7>(env);
-        case 8: return stats_rows_n<8>(env);
-    }
-    return -1;
+    const BlockEnvs be = block_envs(env);
+    if (!be.step) return -1;
+    return ceil_div(env->E, be.step) + (be.fear ? ceil_div(env->E, be.fear) : 0);
 }
 
 gw_status gw_fear_matrix(void *handle, int64_t n, const int32_t *cells, const int32_t *actions,
@@ -3337,7 +3277,7 @@ gw_status gw_fear_matrix(void *handle, int64_t n, const int32_t *cells, const in
     q.tab = env->resp;
     q.HW = env->HW;
     q.W = env->W;
-    q.w_magic = (uint32_t)((((uint64_t)1 << 32) + (uint64_t)env->W - 1) / (uint64_t)env->W);
+    q.w_magic = w_magic(env->W);
     q.cells = cells;
     q.acts = actions;
     q.mdr = mdr;
@@ -3348,19 +3288,8 @@ gw_status gw_fear_matrix(void *handle, int64_t n, const int32_t *cells, const in
     q.feal = feal;
     q.feal_vm = feal_vm;
     q.feal_va = feal_va;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipErrorInvalidValue;
-    switch (env->N) {
-        case 1: return fail(GW_ERR_ARG, "FeAR needs N >= 2");
-        case 2: e = launch_fear_matrix<2>(env, n, q, s); break;
-        case 3: e = launch_fear_matrix<3>(env, n, q, s); break;
-        case 4: e = launch_fear_matrix<4>(env, n, q, s); break;
-        case 5: e = launch_fear_matrix<5>(env, n, q, s); break;
-        case 6: e = launch_fear_matrix<6>(env, n, q, s); break;
-        case 7: e = launch_fear_matrix<7>(env, n, q, s); break;
-        case 8: e = launch_fear_matrix<8>(env, n, q, s); break;
-    }
-    HIP_TRY(e);
+    if (env->N == 1) return fail(GW_ERR_ARG, "FeAR needs N >= 2");
+    HIP_TRY(launch_fear_matrix(env, n, q, static_cast<hipStream_t>(stream)));
     return GW_OK;
 }
 
@@ -3370,45 +3299,6 @@ gw_status gw_obs_patch(void *handle, int32_t P, float *patch, float *final_patch
     if (P < 1 || P > 129) return fail(GW_ERR_ARG, "gw_obs_patch: need 1 <= P <= 129");
     if (!patch && !final_patch) return GW_OK;
     return obs_patch_launch(env, P, patch, final_patch, static_cast<hipStream_t>(stream));
-}
-
-static gw_status obs_patch_launch(Env *env, int32_t P, float *patch, float *final_patch, hipStream_t s) {
-    GW_TRY(wait_fear(env, s));  // async FeAR: the descriptors are written by the world update (joined)
-    gw::PatchArgs a;
-    a.desc = env->desc;
-    a.roadbits = env->roadbits;
-    a.base = env->base;
-    a.patch = patch;
-    a.final_patch = final_patch;
-    a.E = env->E;
-    a.H = env->H;
-    a.W = env->W;
-    a.N = env->N;
-    a.K = env->K;
-    a.P = P;
-    a.variant = env->variant;
-    for (int k = 0; k < GW_MAX_AGENTS; ++k) a.apples[k] = k < env->K ? env->apples[k] : -1;
-    // the map part of each window (P <= 16) comes from a table of every centre's window (built on
-    // first use of this P; 0.5 MB at 32 x 32 and P = 11, 4 MB at 64 x 64 and P = 16);
-    const size_t tb = gw::window_table_bytes(env->H, env->W, P);
-    if (P * P <= 256 && tb <= (size_t)64 << 20) {
-        float *t = nullptr;
-        for (auto &pt : env->ptbls)
-            if (pt.first == P) t = pt.second;
-        if (!t) {
-            GW_TRY(dalloc(env, &t, tb / sizeof(float)));
-            HIP_TRY(gw::build_window_table(a, t, s));
-            // once per (env, P): later calls may come on other streams (a rollout's side stream)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            HIP_TRY(hipStreamIsCapturing(s, &cs));
-            if (cs == hipStreamCaptureStatusNone) HIP_TRY(hipStreamSynchronize(s));
-            env->ptbls.emplace_back(P, t);
-        }
-        a.tbl = t;
-    }
-    gwprof::Span span(env, GW_SPAN_WINDOW);
-    HIP_TRY(gw::launch_windows(a, s));
-    return GW_OK;
 }
 
 gw_status gw_count_sims(void *handle, uint64_t *counter) {
@@ -3459,22 +3349,13 @@ void gw_set_last_error(const char *msg) { g_err = msg ? msg : ""; }
 gw_status gw_graph_replayed(void *handle, void *stream) {
     Env *env = static_cast<Env *>(handle);
     if (!env) return fail(GW_ERR_ARG, "null env");
-    if (env->mode == 4 && env->obs_async && env->qobs.desc) {
+    if (env->mode == PATH_MERGED && env->obs_async && env->qobs.desc) {
         env->obs_queued = true;  // qobs: the last captured step's writer
         env->qobs_prof = false;
         env->last_stream = static_cast<hipStream_t>(stream);
     }
     return GW_OK;
 }
-
-namespace {
-// gw_pipeline_save / gw_pipeline_load: the host-side state a merged-path step leaves behind
-struct PipeState {
-    gw::Params qobs;
-    int32_t qobs_buf, dcur, obs_queued, mode;
-    uint32_t *desc;
-};
-}  // namespace
 
 int64_t gw_pipeline_state_bytes(void) { return (int64_t)sizeof(PipeState); }
 
@@ -3499,7 +3380,7 @@ gw_status gw_pipeline_load(void *handle, const void *buf, void *stream) {
     PipeState st;
     std::memcpy(&st, buf, sizeof(st));
     if (st.mode != env->mode) return fail(GW_ERR_ARG, "gw_pipeline_load: state of another kernel path");
-    if (env->mode != 4 && (env->obs_async || st.obs_queued))
+    if (env->mode != PATH_MERGED && (env->obs_async || st.obs_queued))
         return fail(GW_ERR_STATE, "gw_pipeline_load: only the merged path's async pipeline (or synchronous obs)");
     env->qobs = st.qobs;
     env->qobs_buf = st.qobs_buf;

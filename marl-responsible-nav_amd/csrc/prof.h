@@ -20,9 +20,9 @@ namespace gwprof {
 extern thread_local hipEvent_t t_span_start, t_span_stop, t_bind_stop;
 
 // open a span of `env` if it is profiling (returns false otherwise: nothing to close)
-bool span_begin(void *env, size_t *idx);
-// close it: record (kind, start, stop) if a kernel was launched in it
-void span_end(void *env, size_t idx, int kind);
+bool span_begin(void *env);
+// close the span open now: record (kind, start, stop) if a kernel was launched in it
+void span_end(void *env, int kind);
 
 template <typename F, typename... Args>
 inline void launch(F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
@@ -39,12 +39,11 @@ inline void launch(F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, A
 // scope made through gwprof::launch belongs to one span of `kind`
 struct Span {
     void *env;
-    size_t idx = 0;
     bool open;
     int kind;
-    Span(void *e, int k) : env(e), open(e && span_begin(e, &idx)), kind(k) {}
+    Span(void *e, int k) : env(e), open(e && span_begin(e)), kind(k) {}
     ~Span() {
-        if (open) span_end(env, idx, kind);
+        if (open) span_end(env, kind);
     }
     Span(const Span &) = delete;
     Span &operator=(const Span &) = delete;

@@ -233,18 +233,17 @@ def test_fused_act_block_shape_does_not_change_results(E, monkeypatch):
     env.reset()
     env.step()
     out = {}
-    for sched in ("static",):
-        for w in ("4", "8", "12", "16"):
-            monkeypatch.setenv("GW_ACT_WAVES", w)
-            for rep in range(2):
-                lk = torch.full((sc.K, E, N_ACTIONS), float("nan"), device="cuda")
-                a = torch.full((E, sc.K), -7, dtype=torch.int32, device="cuda")
-                pr = torch.full((sc.K, E, N_ACTIONS), float("nan"), device="cuda")
-                actors.act_env(env, env.out["mask"], True, seed=5, counter=9, logits_out=lk, actions_out=a,
-                               probs_out=pr)
-                assert not torch.isnan(lk).any() and not torch.isnan(pr).any() and bool((a >= 0).all())
-                out[(sched, w, rep)] = (a, pr, lk)
-    ref = out[("static", "16", 0)]
+    for w in ("4", "8", "12", "16"):
+        monkeypatch.setenv("GW_ACT_WAVES", w)
+        for rep in range(2):
+            lk = torch.full((sc.K, E, N_ACTIONS), float("nan"), device="cuda")
+            a = torch.full((E, sc.K), -7, dtype=torch.int32, device="cuda")
+            pr = torch.full((sc.K, E, N_ACTIONS), float("nan"), device="cuda")
+            actors.act_env(env, env.out["mask"], True, seed=5, counter=9, logits_out=lk, actions_out=a,
+                           probs_out=pr)
+            assert not torch.isnan(lk).any() and not torch.isnan(pr).any() and bool((a >= 0).all())
+            out[(w, rep)] = (a, pr, lk)
+    ref = out[("16", 0)]
     for key, v in out.items():
         for x, y in zip(v, ref):
             assert torch.equal(x, y), key
