@@ -45,6 +45,9 @@
 #include "actor_ops.h"
 #include "prof.h"
 #include "measure.h"
+#include "dispatch.h"
+#include "obs_value.h"
+#include "philox.h"
 #include "window_rows.h"
 
 namespace {
@@ -166,35 +169,6 @@ __device__ unsigned long long g_act_clk[1024][16];
     do {                                                                                 \
         if ((GW_AB(p.ab, 8)) && tid == 0 && bid < 1024 && (slot) < 16) g_act_clk[bid][slot] = clock64(); \
     } while (0)
-
-// Philox4x32-10, the same generator as gridenv.hip (keyed draws, graph- and shard-invariant)
-__device__ __forceinline__ uint4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                        uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r > 0) {
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
-
-// obs value of agent n in RL agent k's observation (ma_customenv.py:197-209 reset encoding,
-// :303-322 step encoding incl. the hard-coded relabel list [1, 2, 3, 4]); the same rule as
-// gridenv.hip's obs writer (agent_value)
-__device__ __forceinline__ float agent_value(bool reset, int n, int k, bool on_apple, int variant) {
-    if (reset) return on_apple ? 9.5f : 0.5f;
-    if (on_apple) return (float)(n + 1 + 9);
-    if (variant == 1) return (float)(n + 1);
-    int v = n + 1;
-    if (v >= 1 && v <= 4 && v != k + 1) v = 5;
-    if (v == k + 1) v = 1;
-    return (float)v;
-}
 
 // ---- gw_actor_prepare ----------------------------------------------------------------------
 // map . W1 in row slices: part[k][sl][j] = sum_{c in rows [32 sl, 32 sl + 32)} map[c] * W1[k][c][j]
@@ -420,7 +394,7 @@ __device__ __forceinline__ void act_body(const ActParams &p) {
             for (int n = 0; n < NP - 1; ++n) {
                 const int c = (int)((dw[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
                 pc[1 + n] = valid ? c : -1;
-                pv[1 + n] = agent_value(reset, n, k, c == ac, p.variant);
+                pv[1 + n] = gwobs::agent_value(reset, n, k, c == ac, p.variant);
             }
         }
         // the next tile's descriptor, loaded while this tile computes
@@ -658,7 +632,7 @@ __device__ __forceinline__ void act_body(const ActParams &p) {
             } else {  // draw q of (env, counter, k): actions 4q .. 4q + 3
                 uint64_t ctr = ((uint64_t)p.ctr1 << 32) | p.ctr0;
                 if (p.ctr_dev) ctr += (uint64_t)*p.ctr_dev;
-                const uint4 x = philox((uint32_t)(p.env_offset + e), (uint32_t)ctr,
+                const uint4 x = gwrng::philox((uint32_t)(p.env_offset + e), (uint32_t)ctr,
                                        (uint32_t)k | ((uint32_t)q << 8) | (0xA7u << 24), (uint32_t)(ctr >> 32),
                                        p.key0, p.key1);
                 u[0] = (float)(x.x >> 8) * (1.0f / 16777216.0f);
@@ -1003,7 +977,7 @@ __global__ void __launch_bounds__(64 * L1_WAVES, 4) cnn_l1_kernel(CnnParams p, L
         for (int n = 0; n < NP - 1; ++n) {
             const int c = (int)((dw[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
             pc[1 + n] = valid ? c : -1;
-            pv[1 + n] = agent_value(reset, n, k, c == ac, p.variant);
+            pv[1 + n] = gwobs::agent_value(reset, n, k, c == ac, p.variant);
         }
     }
     // distinct cells (a later slot on the same cell wins), their positions, table columns
@@ -1302,7 +1276,7 @@ __global__ void __launch_bounds__(64 * RARE_WAVES) cnn_rare_kernel(CnnParams p) 
 #pragma unroll
             for (int sl = 0; sl < NP; ++sl) {  // in slot order: a later slot on the same cell wins
                 const int c = sl == 0 ? ac : (int)((dw[(sl - 1) >> 1] >> (16 * ((sl - 1) & 1))) & 0xFFFFu);
-                const float v = sl == 0 ? av : agent_value(reset, sl - 1, k, c == ac, p.variant);
+                const float v = sl == 0 ? av : gwobs::agent_value(reset, sl - 1, k, c == ac, p.variant);
                 const int y = c / p.W - 4 * Y - 2 * (q >> 1), x = c % p.W - 4 * X - 2 * (q & 1);
                 const bool in = c >= 0 && (unsigned)y < 2u && (unsigned)x < 2u;
 #pragma unroll
@@ -1469,7 +1443,7 @@ __global__ void __launch_bounds__(256) wcnn_l1_kernel(CnnParams p, Lists lists) 
         for (int n = 0; n < NP - 1; ++n) {
             const int c = (int)((dw[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
             pc[1 + n] = c;
-            pv[1 + n] = agent_value(reset, n, k, c == ac, p.variant);
+            pv[1 + n] = gwobs::agent_value(reset, n, k, c == ac, p.variant);
         }
     }
     const int ctr = (unsigned)pc[1 + k] < (unsigned)p.HW ? pc[1 + k] : 0;
@@ -1559,7 +1533,7 @@ __device__ __forceinline__ void list_block(const CnnParams &p, int bx, int k) {
             for (int n = 0; n < NP - 1; ++n) {
                 const int c = (int)((dw[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
                 pc[1 + n] = c;
-                pv[1 + n] = agent_value(reset, n, k, c == ac, p.variant);
+                pv[1 + n] = gwobs::agent_value(reset, n, k, c == ac, p.variant);
             }
         }
         const int ctr = (unsigned)pc[1 + k] < (unsigned)p.HW ? pc[1 + k] : 0;
@@ -1760,7 +1734,7 @@ __global__ void __launch_bounds__(64 * WR_WAVES, 2) wcnn_rare_kernel(CnnParams p
 #pragma unroll
             for (int sl = 0; sl < NP; ++sl) {  // in slot order: a later slot on the same cell wins
                 const int c = sl == 0 ? ac : (int)((dw[(sl - 1) >> 1] >> (16 * ((sl - 1) & 1))) & 0xFFFFu);
-                const float v = sl == 0 ? av : agent_value(reset, sl - 1, k, c == ac, p.variant);
+                const float v = sl == 0 ? av : gwobs::agent_value(reset, sl - 1, k, c == ac, p.variant);
                 const bool on = (unsigned)c < (unsigned)p.HW;
                 const int y = (on ? c / p.W : -8) - r0, x = (on ? c % p.W : -8) - c0;
                 const bool in = on && (unsigned)y < 2u && (unsigned)x < 2u;
@@ -1817,6 +1791,15 @@ gw_status check_net(const gw_obs_source &src, const gw_mlp_actors *net, const ch
     return GW_OK;
 }
 
+// the checks both CNN heads end with: the fused channel / layer sizes and the parameter pointers
+gw_status check_cnn_sizes(const gw_cnn_actors *net, const std::string &w) {
+    if (net->c1 != C1 || net->c2 != C2 || net->hidden != HID || net->n_actions != NA)
+        return err(GW_ERR_ARG, w + ": only channels 32-64, hidden 128 and 9 actions are fused");
+    if (!net->conv1_w || !net->conv1_b || !net->conv2_w || !net->conv2_b || !net->lin1_w || !net->lin1_b ||
+        !net->w2 || !net->b2 || !net->w3 || !net->b3)
+        return err(GW_ERR_ARG, w + ": null parameter");
+    return GW_OK;
+}
 
 gw_status check_cnn(const gw_obs_source &src, const gw_cnn_actors *net, const char *who) {
     const std::string w(who);
@@ -1824,12 +1807,16 @@ gw_status check_cnn(const gw_obs_source &src, const gw_cnn_actors *net, const ch
     if (net->H != src.H || net->W != src.W) return err(GW_ERR_ARG, w + ": net H, W != env H, W");
     if (net->H % 4 || net->W % 4 || net->H * net->W > 128 * 32)
         return err(GW_ERR_ARG, w + ": H and W must be multiples of 4, H*W <= 4096");
-    if (net->c1 != C1 || net->c2 != C2 || net->hidden != HID || net->n_actions != NA)
-        return err(GW_ERR_ARG, w + ": only channels 32-64, hidden 128 and 9 actions are fused");
-    if (!net->conv1_w || !net->conv1_b || !net->conv2_w || !net->conv2_b || !net->lin1_w || !net->lin1_b ||
-        !net->w2 || !net->b2 || !net->w3 || !net->b3)
-        return err(GW_ERR_ARG, w + ": null parameter");
-    return GW_OK;
+    return check_cnn_sizes(net, w);
+}
+
+gw_status check_patch_cnn(const gw_obs_source &src, int32_t P, const gw_cnn_actors *net, const char *who) {
+    const std::string w(who);
+    if (P < 4 || P > 16 || P % 4) return err(GW_ERR_ARG, w + ": P must be 4, 8, 12 or 16");
+    if (net->K != src.K) return err(GW_ERR_ARG, w + ": net K != env K");
+    if (net->H != P || net->W != P) return err(GW_ERR_ARG, w + ": net H, W != P");
+    if (src.H * src.W > 128 * 32) return err(GW_ERR_ARG, w + ": H*W must be <= 4096");
+    return check_cnn_sizes(net, w);
 }
 
 CnnParams cnn_params(const gw_obs_source &src, const gw_cnn_actors *net, float *ws) {
@@ -1870,6 +1857,118 @@ gw_mlp_actors cnn_tail(const gw_cnn_actors *net) {  // layers 2-3 as act_kernel'
     return m;
 }
 
+CnnParams wcnn_params(const gw_obs_source &src, int32_t P, const gw_cnn_actors *net, float *ws) {
+    CnnParams p = cnn_params(src, net, ws);   // (its full-grid layout is replaced below)
+    p.PW = P;
+    p.Wq = P / 4;
+    p.P = p.Wq * p.Wq;
+    p.ws = wcnn_ws_layout(ws, src.K, p.P, p.HW, src.E);
+    return p;
+}
+
+// ---- the host launch layer ------------------------------------------------------------------
+// Every prepare and act entry starts here: its pointer arguments (`given`: the entry's own, all
+// non-null), the workspace's alignment, the env's obs view.
+gw_status entry_view(const char *who, void *env, bool given, const float *ws, gw_obs_source &src) {
+    if (!env || !given || !ws) return err(GW_ERR_ARG, std::string(who) + ": null argument");
+    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, std::string(who) + ": ws must be 16-byte aligned");
+    return gw_obs_view(env, &src);
+}
+
+// The kernels are templates of NP = N + 1, the patch slots per (env, agent): f is a generic lambda
+// that launches for std::integral_constant<int, NP>.  gw_create admits 1 <= N <= 8 only, so the
+// error is unreachable for a real handle.
+template <typename F>
+gw_status with_slots(const gw_obs_source &src, const char *who, F &&f) {
+    const bool ok = gw::with_agents(src.N, false, [&](auto n) {
+        f(std::integral_constant<int, decltype(n)::value + 1>{});
+        return true;
+    });
+    return ok ? GW_OK : err(GW_ERR_ARG, std::string(who) + ": N out of range");
+}
+
+// what every act entry takes after (env, net, ws)
+struct ActCall {
+    int training;
+    float tau;
+    uint64_t seed, counter;
+    const int64_t *counter_dev;
+    const float *uniform;
+    const uint16_t *mask;
+    int32_t *actions;
+    float *probs, *logits;
+};
+
+// act_kernel's arguments as far as the three act paths share them: the obs source, the noise key
+// and counter, the outputs, the layer-2/3 images and the tile count.  The input is the whole grid
+// (P = 0, in_dim = HW, no table) until a window path says otherwise; net, the layer-1 source (c1_part,
+// h1, rare_*), zero_n and ab are the caller's.
+ActParams act_params(const gw_obs_source &src, const Ws &img, const ActCall &c) {
+    ActParams p{};
+    p.c1 = img.c1;
+    p.w2img = img.w2;
+    p.w3img = img.w3;
+    p.w2bimg = img.w2b;
+    p.desc = src.desc;
+    p.base = src.base;
+    p.mask = c.mask;
+    p.uniform = c.uniform;
+    p.actions = c.actions;
+    p.probs = c.probs;
+    p.logits = c.logits;
+    p.E = src.E;
+    p.env_offset = src.env_offset;
+    p.N = src.N;
+    p.K = src.K;
+    p.HW = src.H * src.W;
+    p.W = src.W;
+    p.in_dim = p.HW;
+    p.variant = src.variant;
+    p.training = c.training ? 1 : 0;
+    p.tau = c.tau;
+    p.key0 = (uint32_t)c.seed;
+    p.key1 = (uint32_t)(c.seed >> 32);
+    p.ctr0 = (uint32_t)c.counter;
+    p.ctr1 = (uint32_t)(c.counter >> 32);
+    p.ctr_dev = c.counter_dev;
+    for (int k = 0; k < MAXN; ++k) p.apples[k] = src.apples[k];
+    p.tiles = (int)((src.E + TILE - 1) / TILE);
+    return p;
+}
+
+// act_kernel's blocks per agent: a block's `waves` waves take one tile each at a time, and no more
+// blocks than stay resident (`resident` over all K agents)
+int act_blocks(const ActParams &p, int waves, int resident) {
+    const int64_t want = ((int64_t)p.tiles + waves - 1) / waves;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(want, std::max(1, resident / p.K)));
+}
+
+// the layer-2/3 MFMA images alone (prep_images with no row slices: c1 = b1, which the callers
+// rewrite or never read)
+void launch_images(const gw_mlp_actors &net, const Ws &ws, int in_dim, const gw_obs_source &src, hipStream_t s) {
+    PrepParams pp;
+    pp.net = net;
+    pp.HW = in_dim;
+    pp.nslices = 0;
+    pp.ws = ws;
+    pp.base = src.base;
+    hipLaunchKernelGGL(prep_images, dim3(64, src.K), dim3(256), 0, s, pp);
+}
+
+// the launches made so far by entry `who`
+gw_status launched(const char *who) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return err(GW_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return GW_OK;
+}
+
+// GW_WCNN_LIST=scan (A/B): the window CNN head lists its positions with the round-4 chain of layer-1
+// counts, bucket scan and scatter instead of the one fused launch
+bool fused_list() {
+    static const char *list_env = std::getenv("GW_WCNN_LIST");
+    return !(list_env && std::string(list_env) == "scan");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1885,10 +1984,8 @@ int64_t gw_actor_workspace_floats(int32_t in_dim, int32_t K) {
 }
 
 gw_status gw_actor_prepare(void *env, const gw_mlp_actors *net, float *ws, void *stream) {
-    if (!env || !net || !ws) return err(GW_ERR_ARG, "gw_actor_prepare: null argument");
-    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, "gw_actor_prepare: ws must be 16-byte aligned");
     gw_obs_source src;
-    gw_status st = gw_obs_view(env, &src);
+    gw_status st = entry_view("gw_actor_prepare", env, net != nullptr, ws, src);
     if (st != GW_OK) return st;
     if ((st = check_net(src, net, "gw_actor_prepare")) != GW_OK) return st;
     PrepParams p;
@@ -1900,9 +1997,7 @@ gw_status gw_actor_prepare(void *env, const gw_mlp_actors *net, float *ws, void 
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(prep_slices, dim3(p.nslices, src.K), dim3(HID), 0, s, p);
     hipLaunchKernelGGL(prep_images, dim3(64, src.K), dim3(256), 0, s, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, std::string("gw_actor_prepare: ") + hipGetErrorString(e));
-    return GW_OK;
+    return launched("gw_actor_prepare");
 }
 
 gw_status gw_actor_images_view(float *ws, int32_t in_dim, int32_t K, gw_actor_images *out) {
@@ -1920,61 +2015,26 @@ gw_status gw_actor_images_view(float *ws, int32_t in_dim, int32_t K, gw_actor_im
 
 namespace {
 // gw_actor_act (P = 0) and gw_patch_actor_act (P > 0: the P x P window variant)
-gw_status actor_act(const char *who, void *env, int32_t P, const gw_mlp_actors *net, const float *ws, int training,
-                    float tau, uint64_t seed, uint64_t counter, const int64_t *counter_dev, const float *uniform,
-                    const uint16_t *mask,
-                    int32_t *actions, float *probs, float *logits, void *stream) {
-    const std::string w(who);
-    if (!env || !net || !ws || !actions || !probs) return err(GW_ERR_ARG, w + ": null argument");
-    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, w + ": ws must be 16-byte aligned");
+gw_status actor_act(const char *who, void *env, int32_t P, const gw_mlp_actors *net, const float *ws, const ActCall &c,
+                    void *stream) {
     gw_obs_source src;
-    gw_status st = gw_obs_view(env, &src);
+    gw_status st = entry_view(who, env, net && c.actions && c.probs, ws, src);
     if (st != GW_OK) return st;
     if ((st = check_net(src, net, who, P)) != GW_OK) return st;
-    if (!(tau > 0.0f)) return err(GW_ERR_ARG, w + ": tau must be > 0");
-    ActParams p{};
-    p.net = *net;
+    if (!(c.tau > 0.0f)) return err(GW_ERR_ARG, std::string(who) + ": tau must be > 0");
     const Ws wl = ws_layout(const_cast<float *>(ws), src.K);
-    p.c1 = wl.c1;
-    p.w2img = wl.w2;
-    p.w3img = wl.w3;
-    p.w2bimg = wl.w2b;
+    ActParams p = act_params(src, wl, c);
+    p.net = *net;
     if (P == 0) {  // c1 from the row slices (gw_actor_prepare's or a learner's: gw_actor_images)
         p.c1_part = wl.part;
-        p.c1_nslices = (src.H * src.W + 31) / 32;
+        p.c1_nslices = (p.HW + 31) / 32;
+    } else {
+        p.P = P;
+        p.in_dim = P * P;
+        p.tbl = patch_table(const_cast<float *>(ws), src.K);
     }
-    p.desc = src.desc;
-    p.base = src.base;
-    p.mask = mask;
-    p.uniform = uniform;
-    p.h1 = nullptr;
-    p.rare_z = nullptr;
-    p.rare_n = nullptr;
-    p.actions = actions;
-    p.probs = probs;
-    p.logits = logits;
-    p.E = src.E;
-    p.env_offset = src.env_offset;
-    p.N = src.N;
-    p.K = src.K;
-    p.HW = src.H * src.W;
-    p.W = src.W;
-    p.P = P;
-    p.in_dim = P > 0 ? P * P : p.HW;
-    p.tbl = P > 0 ? patch_table(const_cast<float *>(ws), src.K) : nullptr;
-    p.variant = src.variant;
-    p.training = training ? 1 : 0;
-    p.tau = tau;
-    p.key0 = (uint32_t)seed;
-    p.key1 = (uint32_t)(seed >> 32);
-    p.ctr0 = (uint32_t)counter;
-    p.ctr1 = (uint32_t)(counter >> 32);
-    p.ctr_dev = counter_dev;
-    for (int k = 0; k < MAXN; ++k) p.apples[k] = src.apples[k];
     const char *ab = GW_MEASURE_ENV("GW_ACT_AB");
     p.ab = ab ? std::atoi(ab) : 0;
-    const int64_t tiles = (src.E + TILE - 1) / TILE;
-    p.tiles = (int)tiles;
     // GW_ACT_V (A/B): 4 (default) = one 16-wave block per CU, layer 2 as bf16x3 MFMA products;
     // 2 = the same with f32 MFMA (exact products); 0 = two 8-wave blocks per CU, f32 MFMA
     const char *av = std::getenv("GW_ACT_V");
@@ -1986,46 +2046,30 @@ gw_status actor_act(const char *who, void *env, int32_t P, const gw_mlp_actors *
     // VGPRs to co-resident kernels (the rollout's obs writer)
     const char *aw = std::getenv("GW_ACT_WAVES");
     const int awv = aw ? std::atoi(aw) : 0;
-    const bool small = P == 0 && v == 4 && (aw ? awv == 4 : (tiles + 15) / 16 < std::max(1, 256 / src.K) / 2);
+    const bool small = P == 0 && v == 4 && (aw ? awv == 4 : (p.tiles + 15) / 16 < std::max(1, 256 / src.K) / 2);
     const int waves = v == 0 ? 8 : small ? 4 : (P == 0 && v == 4 && (awv == 12 || awv == 8)) ? awv : 16;
     const int resident = v == 0 ? 512 : 256;
-    const int64_t want = (tiles + waves - 1) / waves;
-    const int per_agent = (int)std::max<int64_t>(1, std::min<int64_t>(want, std::max(1, resident / src.K)));
-    const dim3 grid(per_agent, src.K), block(64 * waves);
+    const dim3 grid(act_blocks(p, waves, resident), src.K), block(64 * waves);
     hipStream_t s = static_cast<hipStream_t>(stream);
     gwprof::Span span(env, GW_SPAN_ACT);
-#define ACT_LAUNCH(NP)                                                                   \
-    do {                                                                                 \
-        if (P > 0)                                                                       \
-            gwprof::launch(act_kernel<NP, 16, true, false, true>, grid, block, 0, s, p); \
-        else if (v == 0)                                                                 \
-            gwprof::launch(act_kernel<NP, 8>, grid, block, 0, s, p);                     \
-        else if (v == 4 && small)                                                        \
-            gwprof::launch(act_kernel<NP, 4, true>, grid, block, 0, s, p);               \
-        else if (v == 4 && waves == 12)                                                  \
-            gwprof::launch(act_kernel_lean<NP, 12>, grid, block, 0, s, p);               \
-        else if (v == 4 && waves == 8)                                                   \
-            gwprof::launch(act_kernel_lean<NP, 8>, grid, block, 0, s, p);                \
-        else if (v == 4)                                                                 \
-            gwprof::launch(act_kernel<NP, 16, true>, grid, block, 0, s, p);              \
-        else                                                                             \
-            gwprof::launch(act_kernel<NP, 16>, grid, block, 0, s, p);                    \
-    } while (0)
-    switch (src.N) {
-        case 1: ACT_LAUNCH(2); break;
-        case 2: ACT_LAUNCH(3); break;
-        case 3: ACT_LAUNCH(4); break;
-        case 4: ACT_LAUNCH(5); break;
-        case 5: ACT_LAUNCH(6); break;
-        case 6: ACT_LAUNCH(7); break;
-        case 7: ACT_LAUNCH(8); break;
-        case 8: ACT_LAUNCH(9); break;
-        default: return err(GW_ERR_ARG, w + ": N out of range");
-    }
-#undef ACT_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return GW_OK;
+    st = with_slots(src, who, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        if (P > 0)
+            gwprof::launch(act_kernel<NP, 16, true, false, true>, grid, block, 0, s, p);
+        else if (v == 0)
+            gwprof::launch(act_kernel<NP, 8>, grid, block, 0, s, p);
+        else if (v == 4 && small)
+            gwprof::launch(act_kernel<NP, 4, true>, grid, block, 0, s, p);
+        else if (v == 4 && waves == 12)
+            gwprof::launch(act_kernel_lean<NP, 12>, grid, block, 0, s, p);
+        else if (v == 4 && waves == 8)
+            gwprof::launch(act_kernel_lean<NP, 8>, grid, block, 0, s, p);
+        else if (v == 4)
+            gwprof::launch(act_kernel<NP, 16, true>, grid, block, 0, s, p);
+        else
+            gwprof::launch(act_kernel<NP, 16>, grid, block, 0, s, p);
+    });
+    return st != GW_OK ? st : launched(who);
 }
 }  // namespace
 
@@ -2035,8 +2079,8 @@ gw_status gw_actor_act(void *env, const gw_mlp_actors *net, const float *ws, int
                        uint64_t counter, const int64_t *counter_dev, const float *uniform, const uint16_t *mask,
                        int32_t *actions, float *probs,
                        float *logits, void *stream) {
-    return actor_act("gw_actor_act", env, 0, net, ws, training, tau, seed, counter, counter_dev, uniform, mask, actions, probs,
-                     logits, stream);
+    return actor_act("gw_actor_act", env, 0, net, ws,
+                     ActCall{training, tau, seed, counter, counter_dev, uniform, mask, actions, probs, logits}, stream);
 }
 
 int64_t gw_patch_actor_workspace_floats(int32_t P, int32_t H, int32_t W, int32_t K) {
@@ -2045,10 +2089,8 @@ int64_t gw_patch_actor_workspace_floats(int32_t P, int32_t H, int32_t W, int32_t
 }
 
 gw_status gw_patch_actor_prepare(void *env, int32_t P, const gw_mlp_actors *net, float *ws, void *stream) {
-    if (!env || !net || !ws) return err(GW_ERR_ARG, "gw_patch_actor_prepare: null argument");
-    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, "gw_patch_actor_prepare: ws must be 16-byte aligned");
     gw_obs_source src;
-    gw_status st = gw_obs_view(env, &src);
+    gw_status st = entry_view("gw_patch_actor_prepare", env, net != nullptr, ws, src);
     if (st != GW_OK) return st;
     if ((st = check_net(src, net, "gw_patch_actor_prepare", P)) != GW_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2061,16 +2103,8 @@ gw_status gw_patch_actor_prepare(void *env, int32_t P, const gw_mlp_actors *net,
     tp.W = src.W;
     tp.P = P;
     hipLaunchKernelGGL(prep_patch_table, dim3(src.H * src.W, src.K), dim3(HID), 0, s, tp);
-    PrepParams pp;  // the layer-2/3 MFMA images (prep_images; nslices 0: c1 = b1, unused)
-    pp.net = *net;
-    pp.HW = P * P;
-    pp.nslices = 0;
-    pp.ws = ws_layout(ws, src.K);
-    pp.base = src.base;
-    hipLaunchKernelGGL(prep_images, dim3(64, src.K), dim3(256), 0, s, pp);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, std::string("gw_patch_actor_prepare: ") + hipGetErrorString(e));
-    return GW_OK;
+    launch_images(*net, ws_layout(ws, src.K), P * P, src, s);
+    return launched("gw_patch_actor_prepare");
 }
 
 gw_status gw_patch_actor_act(void *env, int32_t P, const gw_mlp_actors *net, const float *ws, int training, float tau,
@@ -2078,8 +2112,8 @@ gw_status gw_patch_actor_act(void *env, int32_t P, const gw_mlp_actors *net, con
                              const uint16_t *mask,
                              int32_t *actions, float *probs, float *logits, void *stream) {
     if (P < 1) return err(GW_ERR_ARG, "gw_patch_actor_act: P must be >= 1");
-    return actor_act("gw_patch_actor_act", env, P, net, ws, training, tau, seed, counter, counter_dev, uniform, mask, actions,
-                     probs, logits, stream);
+    return actor_act("gw_patch_actor_act", env, P, net, ws,
+                     ActCall{training, tau, seed, counter, counter_dev, uniform, mask, actions, probs, logits}, stream);
 }
 
 
@@ -2088,10 +2122,8 @@ int64_t gw_cnn_workspace_floats(int32_t H, int32_t W, int32_t K, int64_t E) {
 }
 
 gw_status gw_cnn_prepare(void *env, const gw_cnn_actors *net, float *ws, void *stream) {
-    if (!env || !net || !ws) return err(GW_ERR_ARG, "gw_cnn_prepare: null argument");
-    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, "gw_cnn_prepare: ws must be 16-byte aligned");
     gw_obs_source src;
-    gw_status st = gw_obs_view(env, &src);
+    gw_status st = entry_view("gw_cnn_prepare", env, net != nullptr, ws, src);
     if (st != GW_OK) return st;
     if ((st = check_cnn(src, net, "gw_cnn_prepare")) != GW_OK) return st;
     const CnnParams p = cnn_params(src, net, ws);
@@ -2105,47 +2137,30 @@ gw_status gw_cnn_prepare(void *env, const gw_cnn_actors *net, float *ws, void *s
         const Lists l = lists_at(p.ws.unit_off, src.K * p.P, src.K, src.E, L1_ENVS);
         if (hipMemsetAsync(l.ctr, 0, sizeof(int), s) != hipSuccess) return err(GW_ERR_HIP, "gw_cnn_prepare: memset");
     }
-    PrepParams pp;  // the layer-2/3 MFMA images (prep_images; nslices 0: c1 is rewritten below)
-    pp.net = cnn_tail(net);
-    pp.HW = p.HW;
-    pp.nslices = 0;
-    pp.ws = p.ws.mlp;
-    pp.base = src.base;
-    hipLaunchKernelGGL(prep_images, dim3(64, src.K), dim3(256), 0, s, pp);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, std::string("gw_cnn_prepare: ") + hipGetErrorString(e));
-    return GW_OK;
+    launch_images(cnn_tail(net), p.ws.mlp, p.HW, src, s);  // (c1 is rewritten by the act's layer 1)
+    return launched("gw_cnn_prepare");
 }
 
 gw_status gw_cnn_act(void *env, const gw_cnn_actors *net, const float *ws, int training, float tau, uint64_t seed,
                      uint64_t counter, const int64_t *counter_dev, const float *uniform, const uint16_t *mask,
                      int32_t *actions, float *probs,
                      float *logits, void *stream) {
-    if (!env || !net || !ws || !actions || !probs) return err(GW_ERR_ARG, "gw_cnn_act: null argument");
-    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, "gw_cnn_act: ws must be 16-byte aligned");
+    const ActCall c{training, tau, seed, counter, counter_dev, uniform, mask, actions, probs, logits};
     gw_obs_source src;
-    gw_status st = gw_obs_view(env, &src);
+    gw_status st = entry_view("gw_cnn_act", env, net && actions && probs, ws, src);
     if (st != GW_OK) return st;
     if ((st = check_cnn(src, net, "gw_cnn_act")) != GW_OK) return st;
     if (!(tau > 0.0f)) return err(GW_ERR_ARG, "gw_cnn_act: tau must be > 0");
     const CnnParams cp = cnn_params(src, net, const_cast<float *>(ws));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t tiles = (src.E + TILE - 1) / TILE;
     const Lists lists = lists_at(cp.ws.unit_off, src.K * cp.P, src.K, src.E, L1_ENVS);
     const dim3 lgrid((unsigned)lists.nblk, src.K);
     {
         gwprof::Span span(env, GW_SPAN_CNN_L1);
-        switch (src.N) {
-            case 1: gwprof::launch(cnn_l1_kernel<2>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            case 2: gwprof::launch(cnn_l1_kernel<3>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            case 3: gwprof::launch(cnn_l1_kernel<4>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            case 4: gwprof::launch(cnn_l1_kernel<5>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            case 5: gwprof::launch(cnn_l1_kernel<6>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            case 6: gwprof::launch(cnn_l1_kernel<7>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            case 7: gwprof::launch(cnn_l1_kernel<8>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            case 8: gwprof::launch(cnn_l1_kernel<9>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists); break;
-            default: return err(GW_ERR_ARG, "gw_cnn_act: N out of range");
-        }
+        st = with_slots(src, "gw_cnn_act", [&](auto np) {
+            gwprof::launch(cnn_l1_kernel<decltype(np)::value>, lgrid, dim3(64 * L1_WAVES), 0, s, cp, lists);
+        });
+        if (st != GW_OK) return st;
     }
     if (src.K * cp.P > RARE_MAX_NB) return err(GW_ERR_ARG, "gw_cnn_act: K x conv-2 positions above the rare kernels' table");
     {
@@ -2153,66 +2168,23 @@ gw_status gw_cnn_act(void *env, const gw_cnn_actors *net, const float *ws, int t
         gwprof::launch(bucket_scan, dim3(src.K * cp.P), dim3(64), 0, s, cp, lists);
         gwprof::launch(cnn_scatter, lgrid, dim3(L1_ENVS), 0, s, cp, lists);
     }
-#define RARE(NP) gwprof::launch(cnn_rare_kernel<NP>, dim3(RARE_BLOCKS), dim3(64 * RARE_WAVES), 0, s, cp)
     {
         gwprof::Span span(env, GW_SPAN_CNN_RARE);
-        switch (src.N) {
-            case 1: RARE(2); break;
-            case 2: RARE(3); break;
-            case 3: RARE(4); break;
-            case 4: RARE(5); break;
-            case 5: RARE(6); break;
-            case 6: RARE(7); break;
-            case 7: RARE(8); break;
-            default: RARE(9); break;
-        }
+        st = with_slots(src, "gw_cnn_act", [&](auto np) {
+            gwprof::launch(cnn_rare_kernel<decltype(np)::value>, dim3(RARE_BLOCKS), dim3(64 * RARE_WAVES), 0, s, cp);
+        });
+        if (st != GW_OK) return st;
     }
-#undef RARE
-    ActParams p{};
+    ActParams p = act_params(src, cp.ws.mlp, c);
     p.net = cnn_tail(net);
-    p.c1 = cp.ws.mlp.c1;
-    p.w2img = cp.ws.mlp.w2;
-    p.w3img = cp.ws.mlp.w3;
-    p.w2bimg = cp.ws.mlp.w2b;
-    p.desc = src.desc;
-    p.base = src.base;
-    p.mask = mask;
-    p.uniform = uniform;
-    p.h1 = cp.ws.h1;
+    p.h1 = cp.ws.h1;  // layer 1 is cnn_l1_kernel's, plus the rare kernel's recomputed terms
     p.rare_z = cp.ws.rare_z;
     p.rare_n = cp.ws.rare_n;
-    p.actions = actions;
-    p.probs = probs;
-    p.logits = logits;
-    p.E = src.E;
-    p.env_offset = src.env_offset;
-    p.N = src.N;
-    p.K = src.K;
-    p.HW = src.H * src.W;
-    p.W = src.W;
-    p.P = 0;
-    p.in_dim = p.HW;
-    p.tbl = nullptr;
-    p.variant = src.variant;
-    p.training = training ? 1 : 0;
-    p.tau = tau;
-    p.key0 = (uint32_t)seed;
-    p.key1 = (uint32_t)(seed >> 32);
-    p.ctr0 = (uint32_t)counter;
-    p.ctr1 = (uint32_t)(counter >> 32);
-    p.ctr_dev = counter_dev;
-    for (int k = 0; k < MAXN; ++k) p.apples[k] = src.apples[k];
-    p.ab = 0;
-    p.tiles = (int)tiles;
-    const int64_t want = (tiles + 15) / 16;
-    const int per_agent = (int)std::max<int64_t>(1, std::min<int64_t>(want, std::max(1, 256 / src.K)));
     {
         gwprof::Span span(env, GW_SPAN_ACT);
-        gwprof::launch(act_kernel<2, 16, true, true>, dim3(per_agent, src.K), dim3(1024), 0, s, p);
+        gwprof::launch(act_kernel<2, 16, true, true>, dim3(act_blocks(p, 16, 256), src.K), dim3(1024), 0, s, p);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, std::string("gw_cnn_act: ") + hipGetErrorString(e));
-    return GW_OK;
+    return launched("gw_cnn_act");
 }
 
 int64_t gw_patch_cnn_workspace_floats(int32_t P, int32_t H, int32_t W, int32_t K, int64_t E) {
@@ -2220,39 +2192,9 @@ int64_t gw_patch_cnn_workspace_floats(int32_t P, int32_t H, int32_t W, int32_t K
     return wcnn_ws_floats(K, NQ, H * W, E);
 }
 
-}  // extern "C"
-
-namespace {
-gw_status check_patch_cnn(const gw_obs_source &src, int32_t P, const gw_cnn_actors *net, const char *who) {
-    const std::string w(who);
-    if (P < 4 || P > 16 || P % 4) return err(GW_ERR_ARG, w + ": P must be 4, 8, 12 or 16");
-    if (net->K != src.K) return err(GW_ERR_ARG, w + ": net K != env K");
-    if (net->H != P || net->W != P) return err(GW_ERR_ARG, w + ": net H, W != P");
-    if (src.H * src.W > 128 * 32) return err(GW_ERR_ARG, w + ": H*W must be <= 4096");
-    if (net->c1 != C1 || net->c2 != C2 || net->hidden != HID || net->n_actions != NA)
-        return err(GW_ERR_ARG, w + ": only channels 32-64, hidden 128 and 9 actions are fused");
-    if (!net->conv1_w || !net->conv1_b || !net->conv2_w || !net->conv2_b || !net->lin1_w || !net->lin1_b ||
-        !net->w2 || !net->b2 || !net->w3 || !net->b3)
-        return err(GW_ERR_ARG, w + ": null parameter");
-    return GW_OK;
-}
-CnnParams wcnn_params(const gw_obs_source &src, int32_t P, const gw_cnn_actors *net, float *ws) {
-    CnnParams p = cnn_params(src, net, ws);   // (its full-grid layout is replaced below)
-    p.PW = P;
-    p.Wq = P / 4;
-    p.P = p.Wq * p.Wq;
-    p.ws = wcnn_ws_layout(ws, src.K, p.P, p.HW, src.E);
-    return p;
-}
-}  // namespace
-
-extern "C" {
-
 gw_status gw_patch_cnn_prepare(void *env, int32_t P, const gw_cnn_actors *net, float *ws, void *stream) {
-    if (!env || !net || !ws) return err(GW_ERR_ARG, "gw_patch_cnn_prepare: null argument");
-    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, "gw_patch_cnn_prepare: ws must be 16-byte aligned");
     gw_obs_source src;
-    gw_status st = gw_obs_view(env, &src);
+    gw_status st = entry_view("gw_patch_cnn_prepare", env, net != nullptr, ws, src);
     if (st != GW_OK) return st;
     if ((st = check_patch_cnn(src, P, net, "gw_patch_cnn_prepare")) != GW_OK) return st;
     const CnnParams p = wcnn_params(src, P, net, ws);
@@ -2266,16 +2208,8 @@ gw_status gw_patch_cnn_prepare(void *env, int32_t P, const gw_cnn_actors *net, f
             hipMemsetAsync(p.ws.bucket_n, 0, sizeof(int) * src.K * p.P, s) != hipSuccess)
             return err(GW_ERR_HIP, "gw_patch_cnn_prepare: memset");
     }
-    PrepParams pp;  // the layer-2/3 MFMA images (c1 unused)
-    pp.net = cnn_tail(net);
-    pp.HW = P * P;
-    pp.nslices = 0;
-    pp.ws = p.ws.mlp;
-    pp.base = src.base;
-    hipLaunchKernelGGL(prep_images, dim3(64, src.K), dim3(256), 0, s, pp);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, std::string("gw_patch_cnn_prepare: ") + hipGetErrorString(e));
-    return GW_OK;
+    launch_images(cnn_tail(net), p.ws.mlp, P * P, src, s);  // (c1 unused)
+    return launched("gw_patch_cnn_prepare");
 }
 
 // the positions the act recomputes for the env's current descriptors, listed per (agent, position)
@@ -2284,71 +2218,48 @@ gw_status gw_patch_cnn_prepare(void *env, int32_t P, const gw_cnn_actors *net, f
 // the rare kernel read them, and this call (zero = true) zeroes them itself, so a listing that no
 // act consumed (gw_patch_cnn_write_list before an env reset) leaves no counts behind.
 static gw_status patch_cnn_list(void *env, const gw_obs_source &src, const CnnParams &cp, hipStream_t s) {
-    static const char *list_env = std::getenv("GW_WCNN_LIST");
-    const bool fused_list = !(list_env && std::string(list_env) == "scan");
-    if (fused_list) {
+    if (fused_list()) {
         gwprof::Span span(env, GW_SPAN_CNN_L1);
         if (hipMemsetAsync(cp.ws.bucket_n, 0, sizeof(int) * src.K * cp.P, s) != hipSuccess)
             return err(GW_ERR_HIP, "gw_patch_cnn_act: memset");
         const dim3 fgrid((unsigned)((src.E + LR_ENVS - 1) / LR_ENVS), src.K);
-        switch (src.N) {
-            case 1: gwprof::launch(wcnn_list_kernel<2>, fgrid, dim3(256), 0, s, cp); break;
-            case 2: gwprof::launch(wcnn_list_kernel<3>, fgrid, dim3(256), 0, s, cp); break;
-            case 3: gwprof::launch(wcnn_list_kernel<4>, fgrid, dim3(256), 0, s, cp); break;
-            case 4: gwprof::launch(wcnn_list_kernel<5>, fgrid, dim3(256), 0, s, cp); break;
-            case 5: gwprof::launch(wcnn_list_kernel<6>, fgrid, dim3(256), 0, s, cp); break;
-            case 6: gwprof::launch(wcnn_list_kernel<7>, fgrid, dim3(256), 0, s, cp); break;
-            case 7: gwprof::launch(wcnn_list_kernel<8>, fgrid, dim3(256), 0, s, cp); break;
-            case 8: gwprof::launch(wcnn_list_kernel<9>, fgrid, dim3(256), 0, s, cp); break;
-            default: return err(GW_ERR_ARG, "gw_patch_cnn_act: N out of range");
-        }
-    } else {
-        const Lists lists = lists_at(cp.ws.unit_off, src.K * cp.P, src.K, src.E, 256);
-        const dim3 lgrid((unsigned)lists.nblk, src.K);
-        {
-            gwprof::Span span(env, GW_SPAN_CNN_L1);
-            switch (src.N) {
-                case 1: gwprof::launch(wcnn_l1_kernel<2>, lgrid, dim3(256), 0, s, cp, lists); break;
-                case 2: gwprof::launch(wcnn_l1_kernel<3>, lgrid, dim3(256), 0, s, cp, lists); break;
-                case 3: gwprof::launch(wcnn_l1_kernel<4>, lgrid, dim3(256), 0, s, cp, lists); break;
-                case 4: gwprof::launch(wcnn_l1_kernel<5>, lgrid, dim3(256), 0, s, cp, lists); break;
-                case 5: gwprof::launch(wcnn_l1_kernel<6>, lgrid, dim3(256), 0, s, cp, lists); break;
-                case 6: gwprof::launch(wcnn_l1_kernel<7>, lgrid, dim3(256), 0, s, cp, lists); break;
-                case 7: gwprof::launch(wcnn_l1_kernel<8>, lgrid, dim3(256), 0, s, cp, lists); break;
-                case 8: gwprof::launch(wcnn_l1_kernel<9>, lgrid, dim3(256), 0, s, cp, lists); break;
-                default: return err(GW_ERR_ARG, "gw_patch_cnn_act: N out of range");
-            }
-        }
-        gwprof::Span span(env, GW_SPAN_CNN_LIST);
-        gwprof::launch(bucket_scan, dim3(src.K * cp.P), dim3(64), 0, s, cp, lists);
-        gwprof::launch(wcnn_scatter, lgrid, dim3(256), 0, s, cp, lists);
+        return with_slots(src, "gw_patch_cnn_act", [&](auto np) {
+            gwprof::launch(wcnn_list_kernel<decltype(np)::value>, fgrid, dim3(256), 0, s, cp);
+        });
     }
+    const Lists lists = lists_at(cp.ws.unit_off, src.K * cp.P, src.K, src.E, 256);
+    const dim3 lgrid((unsigned)lists.nblk, src.K);
+    {
+        gwprof::Span span(env, GW_SPAN_CNN_L1);
+        const gw_status st = with_slots(src, "gw_patch_cnn_act", [&](auto np) {
+            gwprof::launch(wcnn_l1_kernel<decltype(np)::value>, lgrid, dim3(256), 0, s, cp, lists);
+        });
+        if (st != GW_OK) return st;
+    }
+    gwprof::Span span(env, GW_SPAN_CNN_LIST);
+    gwprof::launch(bucket_scan, dim3(src.K * cp.P), dim3(64), 0, s, cp, lists);
+    gwprof::launch(wcnn_scatter, lgrid, dim3(256), 0, s, cp, lists);
     return GW_OK;
 }
 
+// what the window CNN head's act and listing entries start with
 static gw_status patch_cnn_check(void *env, int32_t P, const gw_cnn_actors *net, const float *ws, gw_obs_source &src,
                                  const char *who) {
-    const std::string w(who);
-    if (!env || !net || !ws) return err(GW_ERR_ARG, w + ": null argument");
-    if (reinterpret_cast<uintptr_t>(ws) & 15u) return err(GW_ERR_ARG, w + ": ws must be 16-byte aligned");
-    gw_status st = gw_obs_view(env, &src);
+    gw_status st = entry_view(who, env, net != nullptr, ws, src);
     if (st != GW_OK) return st;
     if ((st = check_patch_cnn(src, P, net, who)) != GW_OK) return st;
-    if (src.K * (P / 4) * (P / 4) > WR_MAX_NB) return err(GW_ERR_ARG, w + ": K x window positions above the rare kernel's table");
+    if (src.K * (P / 4) * (P / 4) > WR_MAX_NB)
+        return err(GW_ERR_ARG, std::string(who) + ": K x window positions above the rare kernel's table");
     return GW_OK;
 }
 
 // the rare kernel and the actor over the listed positions
 static gw_status patch_cnn_rest(void *env, const gw_obs_source &src, const CnnParams &cp, int32_t P,
-                                const gw_cnn_actors *net, int training, float tau, uint64_t seed, uint64_t counter,
-                                const int64_t *counter_dev, const float *uniform, const uint16_t *mask,
-                                int32_t *actions, float *probs, float *logits, hipStream_t s) {
-    if (!actions || !probs) return err(GW_ERR_ARG, "gw_patch_cnn_act: null argument");
-    if (!(tau > 0.0f)) return err(GW_ERR_ARG, "gw_patch_cnn_act: tau must be > 0");
-    static const char *list_env = std::getenv("GW_WCNN_LIST");
-    const bool fused_list = !(list_env && std::string(list_env) == "scan");
+                                const gw_cnn_actors *net, const ActCall &c, hipStream_t s) {
+    if (!c.actions || !c.probs) return err(GW_ERR_ARG, "gw_patch_cnn_act: null argument");
+    if (!(c.tau > 0.0f)) return err(GW_ERR_ARG, "gw_patch_cnn_act: tau must be > 0");
     static const char *stat_env = GW_MEASURE_ENV("GW_WCNN_STAT");  // diagnostics: the buckets' sizes (synchronises)
-    if (stat_env && *stat_env && fused_list) {
+    if (stat_env && *stat_env && fused_list()) {
         std::vector<int> bn((size_t)src.K * cp.P);
         if (hipStreamSynchronize(s) == hipSuccess &&
             hipMemcpy(bn.data(), cp.ws.bucket_n, sizeof(int) * bn.size(), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -2371,21 +2282,14 @@ static gw_status patch_cnn_rest(void *env, const gw_obs_source &src, const CnnPa
         rstamp = nullptr;
     CnnParams cps = cp;
     cps.stamp = rstamp;
-#define RARE(NP) gwprof::launch(wcnn_rare_kernel<NP>, dim3(WR_BLOCKS), dim3(64 * WR_WAVES), 0, s, cps)
+    gw_status st;
     {
         gwprof::Span span(env, GW_SPAN_CNN_RARE);
-        switch (src.N) {
-            case 1: RARE(2); break;
-            case 2: RARE(3); break;
-            case 3: RARE(4); break;
-            case 4: RARE(5); break;
-            case 5: RARE(6); break;
-            case 6: RARE(7); break;
-            case 7: RARE(8); break;
-            default: RARE(9); break;
-        }
+        st = with_slots(src, "gw_patch_cnn_act", [&](auto np) {
+            gwprof::launch(wcnn_rare_kernel<decltype(np)::value>, dim3(WR_BLOCKS), dim3(64 * WR_WAVES), 0, s, cps);
+        });
+        if (st != GW_OK) return st;
     }
-#undef RARE
     if (rstamp) {
         std::vector<unsigned long long> h((size_t)WR_BLOCKS * 8);
         if (hipStreamSynchronize(s) == hipSuccess &&
@@ -2396,63 +2300,21 @@ static gw_status patch_cnn_rest(void *env, const gw_obs_source &src, const CnnPa
             }
         }
     }
-    ActParams p{};
+    ActParams p = act_params(src, cp.ws.mlp, c);
     p.net = cnn_tail(net);
-    p.c1 = cp.ws.mlp.c1;
-    p.w2img = cp.ws.mlp.w2;
-    p.w3img = cp.ws.mlp.w3;
-    p.w2bimg = cp.ws.mlp.w2b;
-    p.desc = src.desc;
-    p.base = src.base;
-    p.mask = mask;
-    p.uniform = uniform;
-    p.h1 = nullptr;
-    p.rare_z = cp.ws.rare_z;
+    p.rare_z = cp.ws.rare_z;  // layer 1 = the centre's table row + the rare kernel's recomputed terms
     p.rare_n = cp.ws.rare_n;
-    p.actions = actions;
-    p.probs = probs;
-    p.logits = logits;
-    p.E = src.E;
-    p.env_offset = src.env_offset;
-    p.N = src.N;
-    p.K = src.K;
-    p.HW = src.H * src.W;
-    p.W = src.W;
     p.P = P;
     p.in_dim = P * P;
     p.tbl = cp.ws.table;
     p.zero_n = cp.ws.bucket_n;  // the fused listing's bucket counters, read by the rare kernel above
     p.zero_cnt = src.K * cp.P;
-    p.variant = src.variant;
-    p.training = training ? 1 : 0;
-    p.tau = tau;
-    p.key0 = (uint32_t)seed;
-    p.key1 = (uint32_t)(seed >> 32);
-    p.ctr0 = (uint32_t)counter;
-    p.ctr1 = (uint32_t)(counter >> 32);
-    p.ctr_dev = counter_dev;
-    for (int k = 0; k < MAXN; ++k) p.apples[k] = src.apples[k];
-    p.ab = 0;
-    const int64_t tiles = (src.E + TILE - 1) / TILE;
-    p.tiles = (int)tiles;
-    const int64_t want = (tiles + 15) / 16;
-    const int per_agent = (int)std::max<int64_t>(1, std::min<int64_t>(want, std::max(1, 256 / src.K)));
-#define ACTW(NP) gwprof::launch(act_kernel<NP, 16, true, true, true, RSW>, dim3(per_agent, src.K), dim3(1024), 0, s, p)
+    const dim3 grid(act_blocks(p, 16, 256), src.K);
     gwprof::Span span(env, GW_SPAN_ACT);
-    switch (src.N) {
-        case 1: ACTW(2); break;
-        case 2: ACTW(3); break;
-        case 3: ACTW(4); break;
-        case 4: ACTW(5); break;
-        case 5: ACTW(6); break;
-        case 6: ACTW(7); break;
-        case 7: ACTW(8); break;
-        default: ACTW(9); break;
-    }
-#undef ACTW
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, std::string("gw_patch_cnn_act: ") + hipGetErrorString(e));
-    return GW_OK;
+    st = with_slots(src, "gw_patch_cnn_act", [&](auto np) {
+        gwprof::launch(act_kernel<decltype(np)::value, 16, true, true, true, RSW>, grid, dim3(1024), 0, s, p);
+    });
+    return st != GW_OK ? st : launched("gw_patch_cnn_act");
 }
 
 gw_status gw_patch_cnn_act(void *env, int32_t P, const gw_cnn_actors *net, const float *ws, int training, float tau,
@@ -2465,8 +2327,8 @@ gw_status gw_patch_cnn_act(void *env, int32_t P, const gw_cnn_actors *net, const
     const CnnParams cp = wcnn_params(src, P, net, const_cast<float *>(ws));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if ((st = patch_cnn_list(env, src, cp, s)) != GW_OK) return st;
-    return patch_cnn_rest(env, src, cp, P, net, training, tau, seed, counter, counter_dev, uniform, mask, actions,
-                          probs, logits, s);
+    return patch_cnn_rest(env, src, cp, P, net,
+                          ActCall{training, tau, seed, counter, counter_dev, uniform, mask, actions, probs, logits}, s);
 }
 
 gw_status gw_patch_cnn_act_listed(void *env, int32_t P, const gw_cnn_actors *net, const float *ws, int training,
@@ -2477,8 +2339,9 @@ gw_status gw_patch_cnn_act_listed(void *env, int32_t P, const gw_cnn_actors *net
     gw_status st = patch_cnn_check(env, P, net, ws, src, "gw_patch_cnn_act_listed");
     if (st != GW_OK) return st;
     const CnnParams cp = wcnn_params(src, P, net, const_cast<float *>(ws));
-    return patch_cnn_rest(env, src, cp, P, net, training, tau, seed, counter, counter_dev, uniform, mask, actions,
-                          probs, logits, static_cast<hipStream_t>(stream));
+    return patch_cnn_rest(env, src, cp, P, net,
+                          ActCall{training, tau, seed, counter, counter_dev, uniform, mask, actions, probs, logits},
+                          static_cast<hipStream_t>(stream));
 }
 
 gw_status gw_patch_cnn_write_list(void *env, int32_t P, const gw_cnn_actors *net, const float *ws, float *patch,
@@ -2509,27 +2372,13 @@ gw_status gw_patch_cnn_write_list(void *env, int32_t P, const gw_cnn_actors *net
     const dim3 grid(nlist + nrows, src.K);
     hipStream_t s = static_cast<hipStream_t>(stream);
     gwprof::Span span(env, GW_SPAN_WINDOW);
-#define RL(NP)                                                                                      \
-    do {                                                                                            \
-        if (P <= 8) gwprof::launch(rows_list_kernel<NP, 8>, grid, dim3(256), 0, s, a, cp, nlist);  \
-        else if (P <= 12) gwprof::launch(rows_list_kernel<NP, 12>, grid, dim3(256), 0, s, a, cp, nlist); \
-        else gwprof::launch(rows_list_kernel<NP, 16>, grid, dim3(256), 0, s, a, cp, nlist);           \
-    } while (0)
-    switch (src.N) {
-        case 1: RL(2); break;
-        case 2: RL(3); break;
-        case 3: RL(4); break;
-        case 4: RL(5); break;
-        case 5: RL(6); break;
-        case 6: RL(7); break;
-        case 7: RL(8); break;
-        case 8: RL(9); break;
-        default: return err(GW_ERR_ARG, "gw_patch_cnn_write_list: N out of range");
-    }
-#undef RL
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return err(GW_ERR_HIP, std::string("gw_patch_cnn_write_list: ") + hipGetErrorString(e));
-    return GW_OK;
+    st = with_slots(src, "gw_patch_cnn_write_list", [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        if (P <= 8) gwprof::launch(rows_list_kernel<NP, 8>, grid, dim3(256), 0, s, a, cp, nlist);
+        else if (P <= 12) gwprof::launch(rows_list_kernel<NP, 12>, grid, dim3(256), 0, s, a, cp, nlist);
+        else gwprof::launch(rows_list_kernel<NP, 16>, grid, dim3(256), 0, s, a, cp, nlist);
+    });
+    return st != GW_OK ? st : launched("gw_patch_cnn_write_list");
 }
 
 }  // extern "C"

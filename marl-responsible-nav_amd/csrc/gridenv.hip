@@ -32,6 +32,9 @@
 #include "patch_ops.h"
 #include "gridenv.h"
 #include "prof.h"
+#include "dispatch.h"
+#include "obs_value.h"
+#include "philox.h"
 #include "window_rows.h"
 #include "fear_alt_tasks.h"
 
@@ -104,27 +107,6 @@ struct Params {
     int apples[MAXN];
     unsigned long long *sims;  // gw_count_sims: FeAR counterfactual world updates run (null: not counted)
 };
-
-// ---------------------------------------------------------------------------------------
-// Philox4x32-10 (counter-based; every draw is keyed by global env id, episode, step, tag)
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                        uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r > 0) {
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        // one 32x32->64 multiply per product (v_mad_u64_u32) instead of mul_lo + mul_hi
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t lo0 = (uint32_t)p0, hi0 = (uint32_t)(p0 >> 32);
-        const uint32_t lo1 = (uint32_t)p1, hi1 = (uint32_t)(p1 >> 32);
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
 
 __device__ __forceinline__ int div_w(const Params &p, int cell) {
     return (int)__umulhi((uint32_t)cell, p.w_magic);
@@ -464,7 +446,7 @@ __device__ __forceinline__ void spawn_cells(const Params &p, int64_t e, uint32_t
     uint4 r = make_uint4(0, 0, 0, 0);
 #pragma unroll
     for (int d = 0; d < N; ++d) {
-        if ((d & 3) == 0) r = philox(gid, episode, 0xFFFFFFFFu, (3u << 24) | (uint32_t)(d >> 2), p.key0, p.key1);
+        if ((d & 3) == 0) r = gwrng::philox(gid, episode, 0xFFFFFFFFu, (3u << 24) | (uint32_t)(d >> 2), p.key0, p.key1);
         const uint32_t word = ((d & 3) == 0) ? r.x : ((d & 3) == 1) ? r.y : ((d & 3) == 2) ? r.z : r.w;
         const uint32_t j = (uint32_t)(p.F - N + d);
         const int cand = (int)(((uint64_t)word * (uint64_t)(j + 1)) >> 32);
@@ -850,16 +832,6 @@ __global__ void __launch_bounds__(256) reset_kernel(Params p) {
 constexpr int OBS_BE = 16;     // envs per block (max)
 constexpr int OBS_THREADS = 256;
 
-__device__ __forceinline__ float agent_value(bool reset, int n, int k, bool on_apple, int variant) {
-    if (reset) return on_apple ? 9.5f : 0.5f;
-    if (on_apple) return (float)(n + 1 + 9);
-    if (variant == 1) return (float)(n + 1);  // customenv.py:163-166: raw WorldState ids
-    int v = n + 1;
-    if (v >= 1 && v <= 4 && v != k + 1) v = 5;   // other ids -> 5 (all_ids = [1,2,3,4], :314)
-    if (v == k + 1) v = 1;                        // my id -> 1 (:321)
-    return (float)v;
-}
-
 // bf16 bits of an obs value: every value the env writes (-1, 0, 0.5, 1, 5..13, 9.5) is exact in
 // bf16, so the compact format is lossless (the low 16 bits of the f32 are zero)
 __device__ __forceinline__ uint32_t bf16_bits(float v) { return __float_as_uint(v) >> 16; }
@@ -1011,7 +983,7 @@ __device__ __forceinline__ void obs_block(const Params &p, float *__restrict__ o
             for (int n = 0; n < N; ++n) {
                 const int c = (int)((pw[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
                 s_pc[slot + np] = c;
-                s_pv[slot + np] = agent_value(reset, n, k, c == ac, p.variant);
+                s_pv[slot + np] = gwobs::agent_value(reset, n, k, c == ac, p.variant);
                 ++np;
             }
             for (; np < npatch; ++np) s_pc[slot + np] = -1;
@@ -1249,13 +1221,13 @@ __device__ __forceinline__ int draw_action(const Params &p, int64_t e, int n, ui
         if (p.rl) {
             a = p.rl[e * p.K + n];
         } else {
-            const uint4 r = philox(gid, episode, (uint32_t)t, (2u << 24) | (uint32_t)n, p.key0, p.key1);
+            const uint4 r = gwrng::philox(gid, episode, (uint32_t)t, (2u << 24) | (uint32_t)n, p.key0, p.key1);
             a = (int)(((uint64_t)r.x * 9u) >> 32);
         }
     } else if (p.scripted) {
         a = p.scripted[e * (p.N - p.K) + (n - p.K)];
     } else {
-        const uint4 r = philox(gid, episode, (uint32_t)t, (1u << 24) | (uint32_t)n, p.key0, p.key1);
+        const uint4 r = gwrng::philox(gid, episode, (uint32_t)t, (1u << 24) | (uint32_t)n, p.key0, p.key1);
         const int uni = r.x < 0x40000000u;  // random.random() < 0.25 (:441)
         const double u = ((double)(r.y >> 5) * 67108864.0 + (double)(r.z >> 6)) * (1.0 / 9007199254740992.0);
         const int pid = (int)((ctab[pos] >> CT_POL) & 0xFFu);
@@ -2382,29 +2354,12 @@ gw::Params make_params(const Env *env) {
     return p;
 }
 
-// The kernels are templates of the agent count.  This is the only switch over it: f is a generic
-// lambda called with std::integral_constant<int, N>; `bad` is the result for an N outside 1..8.
-template <typename R, typename F>
-R with_agents(int n, R bad, F &&f) {
-    switch (n) {
-        case 1: return f(std::integral_constant<int, 1>{});
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 3: return f(std::integral_constant<int, 3>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 5: return f(std::integral_constant<int, 5>{});
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 7: return f(std::integral_constant<int, 7>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-    }
-    return bad;
-}
-
 // the env's kernel variant: f(N, KMAX, WIDE) as integral constants.  KMAX = 2 for K <= 2, else N
 // (the width of the FeAR task lists); WIDE = the FeAR kernels' block width (fear_wide; the step
 // kernels have no such parameter and ignore it)
 template <typename R, typename F>
 R with_variant(const Env *env, R bad, F &&f) {
-    return with_agents(env->N, bad, [&](auto n) {
+    return gw::with_agents(env->N, bad, [&](auto n) {
         using Two = std::integral_constant<int, 2>;
         if (env->fear_wide) return env->K <= 2 ? f(n, Two{}, std::true_type{}) : f(n, n, std::true_type{});
         return env->K <= 2 ? f(n, Two{}, std::false_type{}) : f(n, n, std::false_type{});
@@ -2493,7 +2448,7 @@ hipError_t launch_fear_alt(const Env *env, const gw::Params &p0, hipStream_t s) 
     const size_t dyn = fear_lds(p);
     const int64_t count = p.e_end - p.e_begin;
     if (count <= 0) return hipSuccess;
-    return with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
+    return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
         gw_launch((gw::fear_alt_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(count, gw::ALT_WAVES)),
                   dim3(gw::ALT_T), dyn, s, p, env->fear_alt);
         return hipGetLastError();
@@ -2501,7 +2456,7 @@ hipError_t launch_fear_alt(const Env *env, const gw::Params &p0, hipStream_t s) 
 }
 
 hipError_t launch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
-    return with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
+    return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
         gw_launch((gw::reset_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(env->E, 256)), dim3(256), 0, s, p);
         return hipGetLastError();
     });
@@ -2509,7 +2464,7 @@ hipError_t launch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
 
 // gw_fear_matrix's kernel (N >= 2: the caller rejects N = 1, FeAR needs a second agent)
 hipError_t launch_fear_matrix(const Env *env, int64_t n_blocks, const gw::FmParams &q, hipStream_t s) {
-    return with_agents(env->N, hipErrorInvalidValue, [&](auto n) -> hipError_t {
+    return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) -> hipError_t {
         constexpr int N = decltype(n)::value;
         if constexpr (N >= 2) {
             gw_launch((gw::fear_matrix_kernel<N>), dim3((unsigned)n_blocks), dim3(128), (size_t)celltab_lds(env->HW), s, q);

@@ -33,6 +33,7 @@
 #include <cstdio>
 
 #include "learner_ops.h"
+#include "obs_value.h"
 #include "philox.h"
 #include "prof.h"
 #include "measure.h"
@@ -937,17 +938,6 @@ int64_t dws_floats(int K, int B, int HW) {
     return (int64_t)(d.adsc - z) + 4;
 }
 
-// obs value of agent n in RL agent k's observation (the obs writer's rule, gridenv.hip agent_value)
-__device__ __forceinline__ float d_agent_value(bool reset, int n, int k, bool on_apple, int variant) {
-    if (reset) return on_apple ? 9.5f : 0.5f;
-    if (on_apple) return (float)(n + 1 + 9);
-    if (variant == 1) return (float)(n + 1);
-    int v = n + 1;
-    if (v >= 1 && v <= 4 && v != k + 1) v = 5;
-    if (v == k + 1) v = 1;
-    return (float)v;
-}
-
 // the patched cells of agent k's obs from descriptor words d (wsel 0: the obs, 1: the terminal
 // obs, words 8-11), in the obs writer's order (the own apple, then agents 0 .. N-1; a later
 // patch of the same cell overrides an earlier one), reduced to the surviving cells, as deltas
@@ -972,7 +962,7 @@ __device__ __forceinline__ int d_patches(const DQ &q, const uint32_t (&d)[NDW], 
         const uint32_t w = wsel == 0 ? d[n >> 1] : d[8 + (n >> 1)];
         const int c = (int)((w >> (16 * (n & 1))) & 0xFFFFu);
         pc[np] = c;
-        pv[np] = d_agent_value(reset, n, k, c == ac, q.variant);
+        pv[np] = gwobs::agent_value(reset, n, k, c == ac, q.variant);
         ++np;
     }
     float bv[NPM];

@@ -24,6 +24,7 @@
 #include "patch_ops.h"
 #include "prof.h"
 #include "measure.h"
+#include "obs_value.h"
 #include "window_rows.h"
 
 namespace {
@@ -32,16 +33,6 @@ constexpr int THREADS = 256, MAXP = GW_MAX_AGENTS + 1, MAXPL = 4;  // MAXPL: P *
 // PB: envs per block (a template parameter: 32, or 64 where the LDS leaves room for enough blocks)
 constexpr uint32_t D_RESET = 1u, D_WRITE = 2u, D_FINAL = 4u;
 constexpr int NDESC = 12;
-
-__device__ __forceinline__ float agent_value(bool reset, int n, int k, bool on_apple, int variant) {
-    if (reset) return on_apple ? 9.5f : 0.5f;
-    if (on_apple) return (float)(n + 1 + 9);
-    if (variant == 1) return (float)(n + 1);
-    int v = n + 1;
-    if (v >= 1 && v <= 4 && v != k + 1) v = 5;
-    if (v == k + 1) v = 1;
-    return (float)v;
-}
 
 __device__ __forceinline__ float map_value(const uint32_t *road, int H, int W, int r, int q) {
     if (r < 0 || r >= H || q < 0 || q >= W) return -1.0f;
@@ -131,7 +122,7 @@ __global__ void __launch_bounds__(THREADS) window_kernel(gw::PatchArgs a, unsign
                 if (n >= N) break;
                 const int c = (int)((words[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
                 cell[u] = c;
-                val[u] = agent_value(reset, n, k, c == ac, a.variant);
+                val[u] = gwobs::agent_value(reset, n, k, c == ac, a.variant);
                 ++u;
             }
             for (int i = 0; i < np; ++i) {

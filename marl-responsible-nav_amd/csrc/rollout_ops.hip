@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <string>
 
+#include "obs_value.h"
 #include "philox.h"
 #include "rollout_ops.h"
 
@@ -221,16 +222,6 @@ __global__ void __launch_bounds__(256) replay_gather_kernel(
 constexpr int DESC_WORDS = 12;  // gridenv.hip NDESC
 constexpr uint32_t DF_RESET = 1u;
 
-__device__ __forceinline__ float desc_agent_value(bool reset, int n, int k, bool on_apple, int variant) {
-    if (reset) return on_apple ? 9.5f : 0.5f;
-    if (on_apple) return (float)(n + 1 + 9);
-    if (variant == 1) return (float)(n + 1);
-    int v = n + 1;
-    if (v >= 1 && v <= 4 && v != k + 1) v = 5;
-    if (v == k + 1) v = 1;
-    return (float)v;
-}
-
 struct DescSrc {
     const float *base;
     int apples[GW_MAX_AGENTS];
@@ -258,7 +249,7 @@ __device__ __forceinline__ int desc_patches(const DescSrc &q, const uint32_t (&d
         const uint32_t w = which == 0 ? d[n >> 1] : d[8 + (n >> 1)];
         const int c = (int)((w >> (16 * (n & 1))) & 0xFFFFu);
         pc[np] = c;
-        pv[np] = desc_agent_value(reset, n, k, c == ac, q.variant);
+        pv[np] = gwobs::agent_value(reset, n, k, c == ac, q.variant);
         ++np;
     }
     return np;

@@ -9,6 +9,7 @@
 
 #include <cstdint>
 
+#include "obs_value.h"
 #include "patch_ops.h"
 
 namespace gwrows {
@@ -16,17 +17,6 @@ namespace gwrows {
 constexpr uint32_t D_RESET = 1u, D_WRITE = 2u, D_FINAL = 4u;  // obs descriptor flags (gridenv.hip)
 constexpr int NDESC = 12;                                     // u32 words per obs descriptor
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// the obs writer's value of agent n's cell in agent k's observation (gridenv.hip obs_block)
-__device__ __forceinline__ float agent_value(bool reset, int n, int k, bool on_apple, int variant) {
-    if (reset) return on_apple ? 9.5f : 0.5f;
-    if (on_apple) return (float)(n + 1 + 9);
-    if (variant == 1) return (float)(n + 1);
-    int v = n + 1;
-    if (v >= 1 && v <= 4 && v != k + 1) v = 5;
-    if (v == k + 1) v = 1;
-    return (float)v;
-}
 
 // block bx of agent k (grid ((E P + 511) / 512, K), 256 threads); s_rows: the block's LDS,
 // [WAVES][64 rows x MAXW / 4 float4]
@@ -119,7 +109,7 @@ __device__ __forceinline__ void rows_block(const gw::PatchArgs &a, uint32_t bx, 
 #pragma unroll
             for (int n = 0; n < NP - 1; ++n) {
                 const int c = (int)((wd[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
-                patch(c, agent_value(reset, n, k, c == ac, a.variant));
+                patch(c, gwobs::agent_value(reset, n, k, c == ac, a.variant));
             }
         }
         __builtin_amdgcn_wave_barrier();  // (a wave's LDS operations complete in order)

@@ -30,7 +30,8 @@ HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_op
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
                                    os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "measure.h"),
-                                   os.path.join(CSRC, "fear_alt_tasks.h")]
+                                   os.path.join(CSRC, "fear_alt_tasks.h"), os.path.join(CSRC, "dispatch.h"),
+                                   os.path.join(CSRC, "obs_value.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
