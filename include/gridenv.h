@@ -301,6 +301,29 @@ gw_status gw_set_obs_async(void *env, int enable);
 enum { GW_OBS_F32 = 0, GW_OBS_BF16 = 1 };
 gw_status gw_set_obs_dtype(void *env, int dtype);
 
+/* The delta obs writer (default off).  An observation is the static map plus at most N + 1 patched
+ * cells per (env, RL agent), so a buffer that already holds an obs this env wrote differs from the
+ * next obs written there in at most 2 K (N + 1) cells per env.  While on, the env keeps a table of
+ * GW_OBS_DESTS obs destinations it wrote last (least recently used evicted): the pointer, the dtype,
+ * a device copy of the descriptors written there and the last writer's event.  A gw_step whose
+ * gw_step_out.obs has a valid entry stores only the changed cells (obs_delta_kernel, ordered after
+ * the previous writer of that buffer); any other step runs the full writer, which fills the entry.
+ * The results are the same bit for bit.  final_obs always takes the full writer's path.
+ * THE CALLER'S PROMISE while on: between two gw_steps that write the same obs pointer nothing else
+ * writes those bytes (a fill, a copy into the buffer, another env, freeing the buffer and getting
+ * the address back for another one), or the caller calls gw_obs_dest_forget(env, ptr) before the
+ * second step (ptr NULL: every entry).  The library cannot see such writes: a pointer says nothing
+ * about the bytes behind it.  marlnav.VecGridEnv keeps that promise for writes torch can see (it
+ * holds the tensor and compares its version counter); writes through raw pointers need the call.
+ * Always the full writer, and no entry survives: the merged kernel path, bf16 obs, gw_set_obs_dtype,
+ * gw_reset, gw_pipeline_load, gw_graph_replayed (call one of the two after replaying a graph of
+ * captured steps, or forget), and steps recorded while the stream is capturing.
+ * gw_obs_delta_counts: out[0] / out[1] = gw_steps whose obs the full / the delta writer wrote. */
+#define GW_OBS_DESTS 8
+gw_status gw_set_obs_delta(void *env, int on);
+gw_status gw_obs_dest_forget(void *env, const void *ptr);
+gw_status gw_obs_delta_counts(void *env, int64_t out[2]);
+
 /* The FeAR kernel's envs per block, before the first gw_reset (it fixes gw_stats_rows: size the
  * stats buffer after it): wide = 1 (the default: half the resident waves, best beside the full-obs
  * writer), 0 = narrow (twice the waves, best where FeAR is on the critical path: an env that writes

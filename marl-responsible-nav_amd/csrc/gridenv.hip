@@ -34,6 +34,7 @@
 #include "prof.h"
 #include "dispatch.h"
 #include "obs_value.h"
+#include "obs_dest.h"
 #include "philox.h"
 #include "window_rows.h"
 #include "fear_alt_tasks.h"
@@ -959,6 +960,10 @@ __device__ __forceinline__ void obs_block(const Params &p, float *__restrict__ o
     const int64_t e0 = p.e_begin + bid * p.obs_be;
     if (e0 >= p.e_end) return;  // uniform per block
     const int nenv = (int)min((int64_t)p.obs_be, p.e_end - e0);
+    if (!obs) {  // the terminal obs alone (beside the delta writer): few blocks hold an env that ended
+        const bool fin = final_obs && tid < nenv && (p.desc[(e0 + tid) * NDESC + 4] & D_FINAL) != 0;
+        if (!__syncthreads_or(fin)) return;
+    }
     for (int w = tid; w < nroad; w += T) s_road[w] = p.tb.roadbits[w];
     // patches: one thread per (which, env, k)
     if (tid < 2 * p.obs_be * K) {
@@ -1143,6 +1148,108 @@ __global__ void __launch_bounds__(OBS_THREADS) obs_kernel(Params p, float *__res
                                                           float *__restrict__ final_obs) {
     extern __shared__ uint32_t obs_lds[];
     obs_block<OBS_THREADS, VEC4, NT, BF16>(p, obs, final_obs, blockIdx.x, obs_lds);
+}
+
+// ---------------------------------------------------------------------------------------
+// The delta writer (gw_set_obs_delta): the f32 step obs of a destination the env wrote last.
+// An obs is the map plus at most N + 1 patched cells per (env, agent), so a buffer that holds the
+// obs of the descriptors `saved` differs from this step's obs in at most 2 (N + 1) cells per
+// (env, agent): the old patched cells go back to the map, the new ones get their values.
+// One thread per (env, agent); a block owns DELTA_T / K envs.  Every address is written at most
+// once per launch (no restore-then-overwrite between threads or stores): a new cell is stored by
+// its last slot only (a later slot overrides, obs_block's rule), an old cell only if it is no new
+// cell, once; cells whose value stays are skipped.  Then `saved` takes this step's descriptors
+// (behind a block barrier: the env's K threads have read the old ones).
+// ---------------------------------------------------------------------------------------
+constexpr int DELTA_T = 256;
+constexpr int NPATCH_MAX = MAXN + 1;
+
+struct PatchSet {
+    int c[NPATCH_MAX];    // slot 0 the apple, 1 + n agent n; -1: unused
+    float v[NPATCH_MAX];
+};
+
+// the patch slots of RL agent k's step obs (obs_block's decoding and order)
+__device__ __forceinline__ void decode_patches(const Params &p, const uint4 &cells, uint32_t f, int k, PatchSet &ps) {
+    const bool reset = (f & D_RESET) != 0;
+    const uint32_t apples = (f >> 8) & 0xFFu;
+    int ak = -1;
+#pragma unroll
+    for (int j = 0; j < MAXN; ++j) ak = j == k ? p.apples[j] : ak;
+    const int ac = ((apples >> k) & 1u) && (unsigned)ak < (unsigned)p.HW ? ak : -1;
+    float av = 0.0f;
+    if (ac >= 0) {
+        av = p.tb.base[ac] + 9.0f;
+        if (!reset && av == (float)(k + 1)) av = 1.0f;  // relabel of :321 (apple on a wall, K = 8)
+    }
+    ps.c[0] = ac;
+    ps.v[0] = av;
+    const uint32_t w[4] = {cells.x, cells.y, cells.z, cells.w};
+#pragma unroll
+    for (int n = 0; n < MAXN; ++n) {
+        const int c = (int)((w[n >> 1] >> (16 * (n & 1))) & 0xFFFFu);
+        ps.c[1 + n] = n < p.N ? c : -1;
+        ps.v[1 + n] = gwobs::agent_value(reset, n, k, c == ac, p.variant);
+    }
+}
+
+__global__ void __launch_bounds__(DELTA_T) obs_delta_kernel(Params p, float *__restrict__ obs,
+                                                            uint32_t *__restrict__ saved) {
+    const int K = p.K, HW = p.HW;
+    const int eb = DELTA_T / K;  // envs per block
+    const int el = threadIdx.x / K, k = threadIdx.x - el * K;
+    const int64_t e = p.e_begin + (int64_t)blockIdx.x * eb + el;
+    const bool live = el < eb && e < p.e_end;
+    uint4 nw[3], ocells;
+    uint32_t nf = 0, of = 0;
+    if (live) {
+        const uint4 *dn = reinterpret_cast<const uint4 *>(p.desc + e * NDESC);
+        const uint4 *ds = reinterpret_cast<const uint4 *>(saved + e * NDESC);
+        nw[0] = dn[0];
+        nw[1] = dn[1];
+        nw[2] = dn[2];
+        nf = nw[1].x;
+        ocells = ds[0];
+        of = saved[e * NDESC + 4];
+    }
+    __syncthreads();
+    if (!live || !(nf & D_WRITE)) return;  // not written this step: the buffer and `saved` stay
+    if (k == 0) {
+        uint4 *ds = reinterpret_cast<uint4 *>(saved + e * NDESC);
+        ds[0] = nw[0];
+        ds[1] = nw[1];
+        ds[2] = nw[2];
+    }
+    PatchSet nu, od;
+    decode_patches(p, nw[0], nf, k, nu);
+    decode_patches(p, ocells, of, k, od);
+    float *o = obs + ((int64_t)k * p.E + e) * HW;
+#pragma unroll
+    for (int q = 0; q < NPATCH_MAX; ++q) {  // the new patched cells: their final values
+        const int c = nu.c[q];
+        bool st = (unsigned)c < (unsigned)HW;
+#pragma unroll
+        for (int q2 = q + 1; q2 < NPATCH_MAX; ++q2) st = st && nu.c[q2] != c;  // a later slot overrides
+        bool held = false;  // the buffer holds a patch value at c (the last old slot's)
+        float ov = 0.0f;
+#pragma unroll
+        for (int q2 = 0; q2 < NPATCH_MAX; ++q2) {
+            const bool m = od.c[q2] == c;
+            held = held || m;
+            ov = m ? od.v[q2] : ov;
+        }
+        if (st && !(held && ov == nu.v[q])) o[c] = nu.v[q];  // (a patch value is never a map value)
+    }
+#pragma unroll
+    for (int q = 0; q < NPATCH_MAX; ++q) {  // the old patched cells that are no new ones: the map
+        const int c = od.c[q];
+        bool st = (unsigned)c < (unsigned)HW;
+#pragma unroll
+        for (int q2 = 0; q2 < q; ++q2) st = st && od.c[q2] != c;  // once
+#pragma unroll
+        for (int q2 = 0; q2 < NPATCH_MAX; ++q2) st = st && nu.c[q2] != c;
+        if (st) o[c] = ((p.tb.roadbits[c >> 5] >> (c & 31)) & 1u) ? 0.0f : -1.0f;
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2130,6 +2237,15 @@ struct Env {
     gw::Params qobs;
     uint32_t *desc_buf[2] = {nullptr, nullptr};
     int dcur = 0;
+    // gw_set_obs_delta: the obs destinations the env wrote last (obs_dest.h) and, per table slot,
+    // the device copy of the descriptors written there, the last writer's event and its stream
+    bool obs_delta = false;
+    gwdest::Table dests;
+    uint32_t *dest_desc[gwdest::SLOTS] = {nullptr};
+    hipEvent_t dest_ev[gwdest::SLOTS] = {nullptr};
+    hipStream_t dest_stream[gwdest::SLOTS] = {nullptr};
+    bool dest_written[gwdest::SLOTS] = {false};
+    int64_t n_obs_full = 0, n_obs_delta = 0;  // gw_step obs writes by the full / the delta writer
     // tables
     uint8_t *okmask = nullptr, *policy = nullptr, *mdr = nullptr;
     double *cdf = nullptr, *resp = nullptr;
@@ -2522,21 +2638,98 @@ hipError_t launch_obs_range(const Env *env, const gw::Params &p, float *obs, flo
 // dispatches one kernel's workgroups ahead of a later kernel of another queue, so a single
 // long writer holds the CUs until its last workgroup is placed; between chunk launches the
 // caller stream's kernels (the next actor) get their turn.
+// The chunks of p's env range, for the full and the delta writer alike: how many, and chunk i's
+// params (whole obs_kernel blocks per chunk).
+int64_t obs_chunk_count(const Env *env, const gw::Params &p) {
+    const int64_t blocks = ceil_div(p.e_end - p.e_begin, env->obs_be);
+    return std::max<int64_t>(1, std::min<int64_t>(env->obs_chunks, blocks));
+}
+
+gw::Params obs_chunk(const Env *env, const gw::Params &p, int64_t i, int64_t c) {
+    const int64_t blocks = ceil_div(p.e_end - p.e_begin, env->obs_be);
+    gw::Params q = p;
+    q.e_begin = p.e_begin + blocks * i / c * env->obs_be;
+    q.e_end = std::min(p.e_end, p.e_begin + blocks * (i + 1) / c * env->obs_be);
+    return q;
+}
+
 hipError_t launch_obs(Env *env, const gw::Params &p, float *obs, float *final_obs, hipStream_t s) {
     if (!obs && !final_obs) return hipSuccess;
-    const int64_t n = p.e_end - p.e_begin;
-    if (n <= 0) return hipSuccess;
-    const int64_t blocks = ceil_div(n, env->obs_be);
-    const int64_t c = std::max<int64_t>(1, std::min<int64_t>(env->obs_chunks, blocks));
+    if (p.e_end - p.e_begin <= 0) return hipSuccess;
+    const int64_t c = obs_chunk_count(env, p);
     for (int64_t i = 0; i < c; ++i) {
         if (i > 0) prof_span_split(env, GW_SPAN_OBS);  // profiled: one span per chunk
-        gw::Params q = p;
-        q.e_begin = p.e_begin + blocks * i / c * env->obs_be;
-        q.e_end = std::min(p.e_end, p.e_begin + blocks * (i + 1) / c * env->obs_be);
+        const gw::Params q = obs_chunk(env, p, i, c);
         const hipError_t e = launch_obs_range(env, q, obs, final_obs, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// A gw_step's obs writer on s, by destination (gw_set_obs_delta).  p.out.obs has a valid table
+// slot: the env wrote that buffer last, in f32, and the slot's saved descriptors say what it
+// holds, so the delta writer patches the changed cells (final_obs keeps the full writer: rows of
+// the few envs that ended).  Anything else is the full writer, which also fills the slot (its
+// saved descriptors are copied first on s, so the launch that carries the pipeline's stop event
+// stays the last one).  Either writer waits for the slot's last writer when that ran on another
+// stream, and leaves its own event.  Never while s is capturing: a replay writes buffers behind
+// the host's back, so a capture forgets every destination and records full writes
+// (own_stream: s is one of the env's obs streams, which no caller can capture: not asked).
+gw_status launch_obs_dest(Env *env, const gw::Params &p, hipStream_t s, bool own_stream = false) {
+    float *obs = p.out.obs, *final_obs = p.out.final_obs;
+    const bool able = env->obs_delta && env->mode == PATH_DEFER && !env->obs_bf16 && obs && !p.rmask &&
+                      p.e_begin == 0 && p.e_end == env->E;
+    bool capturing = false;
+    if (able && !own_stream) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(s, &cs));
+        capturing = cs != hipStreamCaptureStatusNone;
+    }
+    if (!able || capturing) {
+        if (capturing) env->dests.forget(nullptr);
+        else if (obs) env->dests.forget(obs);  // written outside the table's terms
+        if (obs) env->n_obs_full++;
+        HIP_TRY(launch_obs(env, p, obs, final_obs, s));
+        return GW_OK;
+    }
+    int i = env->dests.find(obs, GW_OBS_F32);
+    const bool delta = i >= 0;
+    if (!delta) i = env->dests.claim(obs, GW_OBS_F32);
+    if (!env->dest_desc[i]) {
+        env->dests.slot[i].valid = false;  // until its buffers exist
+        GW_TRY(dalloc(env, &env->dest_desc[i], (size_t)env->E * gw::NDESC));
+        HIP_TRY(hipEventCreateWithFlags(&env->dest_ev[i], env->sync_flags));
+        env->dests.slot[i].valid = true;
+    }
+    if (env->dest_written[i] && env->dest_stream[i] != s) HIP_TRY(hipStreamWaitEvent(s, env->dest_ev[i], 0));
+    if (delta) {
+        env->n_obs_delta++;
+        if (final_obs) HIP_TRY(launch_obs(env, p, nullptr, final_obs, s));
+        // GW_OBS_CHUNKS chunks it as the full writer (launch_obs): the same launches per step, so
+        // the next actor's kernels are still dispatched between them
+        // (the same env ranges, obs_chunk: the kernel takes any e_begin)
+        const int eb = gw::DELTA_T / env->K;
+        const int64_t c = obs_chunk_count(env, p);
+        for (int64_t j = 0; j < c; ++j) {
+            if (j > 0) prof_span_split(env, GW_SPAN_OBS);  // profiled: one span per chunk
+            const gw::Params q = obs_chunk(env, p, j, c);
+            gw_launch(gw::obs_delta_kernel, dim3((unsigned)ceil_div(q.e_end - q.e_begin, eb)), dim3(gw::DELTA_T), 0, s,
+                      q, obs, env->dest_desc[i]);
+            HIP_TRY(hipGetLastError());
+        }
+    } else {
+        env->n_obs_full++;
+        const int64_t n16 = (int64_t)env->E * gw::NDESC / 4;
+        const unsigned grid = (unsigned)std::min<int64_t>((n16 + 255) / 256, 2048);
+        gw_launch(gw::copy16_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const uint4 *>(p.desc),
+                  reinterpret_cast<uint4 *>(env->dest_desc[i]), n16);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_obs(env, p, obs, final_obs, s));
+    }
+    HIP_TRY(hipEventRecord(env->dest_ev[i], s));
+    env->dest_stream[i] = s;
+    env->dest_written[i] = true;
+    return GW_OK;
 }
 
 // launch the queued obs_kernel on the obs stream, after its world update and (after != null)
@@ -2568,7 +2761,7 @@ gw_status flush_obs(Env *env, hipEvent_t after, hipStream_t on = nullptr) {
         SpanGuard span(env, prof, GW_SPAN_OBS);
         GW_TRY(span.status);
         BindStop bind(prof ? nullptr : done);  // untimed: obs_done carried by the writer's launch
-        HIP_TRY(launch_obs(env, q, q.out.obs, q.out.final_obs, os));
+        GW_TRY(launch_obs_dest(env, q, os, true));
     }
     if (prof) HIP_TRY(hipEventRecord(done, os));
     env->obs_pending[env->qobs_buf] = true;
@@ -2734,8 +2927,7 @@ gw_status fear_stage(Env *env, const gw::Params &p, hipStream_t s) {
 gw_status write_obs(Env *env, const gw::Params &p, hipStream_t s) {
     SpanGuard span(env, env->profiling, GW_SPAN_OBS);
     GW_TRY(span.status);
-    HIP_TRY(launch_obs(env, p, p.out.obs, p.out.final_obs, s));
-    return GW_OK;
+    return launch_obs_dest(env, p, s);
 }
 
 // ---- gw_step: the four paths ----
@@ -3023,6 +3215,7 @@ gw_status gw_reset(void *handle, const uint8_t *env_mask, const int32_t *spawn_c
     p.out.mask = mask;
     hipStream_t s = static_cast<hipStream_t>(stream);
     GW_TRY(wait_obs(env, s));  // async obs: the descriptors are rewritten in place below
+    env->dests.forget(nullptr);  // the reset writes a destination outside the table's bookkeeping
     HIP_TRY(launch_reset(env, p, s));
     HIP_TRY(launch_obs(env, p, obs, nullptr, s));
     env->initialized = true;
@@ -3088,6 +3281,7 @@ gw_status gw_set_obs_dtype(void *handle, int dtype) {
     const bool bf = dtype == GW_OBS_BF16;
     // an obs_kernel still queued or in flight was sized for the old format: drain it first
     if (bf != env->obs_bf16) GW_TRY(drain_writers(env));
+    env->dests.forget(nullptr);  // what the buffers hold changes meaning with the format
     // bf16 writer: ~64 KB of obs per block (C3: 16 envs, 4.3 TB/s; 4 envs 3.4, 8 envs 4.2;
     // C4: 4 envs; profiles/r1_bf16); f32: the create-time default
     env->obs_be = bf ? std::max(1, std::min(gw::OBS_BE, 32768 / std::max(1, env->K * env->HW)))
@@ -3304,6 +3498,7 @@ void gw_set_last_error(const char *msg) { g_err = msg ? msg : ""; }
 gw_status gw_graph_replayed(void *handle, void *stream) {
     Env *env = static_cast<Env *>(handle);
     if (!env) return fail(GW_ERR_ARG, "null env");
+    env->dests.forget(nullptr);  // the replay's writers wrote their buffers behind the table's back
     if (env->mode == PATH_MERGED && env->obs_async && env->qobs.desc) {
         env->obs_queued = true;  // qobs: the last captured step's writer
         env->qobs_prof = false;
@@ -3337,6 +3532,7 @@ gw_status gw_pipeline_load(void *handle, const void *buf, void *stream) {
     if (st.mode != env->mode) return fail(GW_ERR_ARG, "gw_pipeline_load: state of another kernel path");
     if (env->mode != PATH_MERGED && (env->obs_async || st.obs_queued))
         return fail(GW_ERR_STATE, "gw_pipeline_load: only the merged path's async pipeline (or synchronous obs)");
+    env->dests.forget(nullptr);  // a replayed graph wrote obs buffers behind the table's back
     env->qobs = st.qobs;
     env->qobs_buf = st.qobs_buf;
     env->dcur = st.dcur;
@@ -3344,6 +3540,29 @@ gw_status gw_pipeline_load(void *handle, const void *buf, void *stream) {
     env->obs_queued = st.obs_queued != 0;
     env->qobs_prof = false;
     env->last_stream = static_cast<hipStream_t>(stream);
+    return GW_OK;
+}
+
+gw_status gw_set_obs_delta(void *handle, int on) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "null env");
+    env->dests.forget(nullptr);
+    env->obs_delta = on != 0;
+    return GW_OK;
+}
+
+gw_status gw_obs_dest_forget(void *handle, const void *ptr) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "null env");
+    env->dests.forget(ptr);
+    return GW_OK;
+}
+
+gw_status gw_obs_delta_counts(void *handle, int64_t out[2]) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env || !out) return fail(GW_ERR_ARG, "null argument");
+    out[0] = env->n_obs_full;
+    out[1] = env->n_obs_delta;
     return GW_OK;
 }
 
@@ -3373,6 +3592,8 @@ void gw_destroy(void *handle) {
         if (e) (void)hipEventDestroy(e);
     if (env->world_ev) (void)hipEventDestroy(env->world_ev);
     if (env->fear_ev) (void)hipEventDestroy(env->fear_ev);
+    for (hipEvent_t e : env->dest_ev)
+        if (e) (void)hipEventDestroy(e);
     for (void *p : env->allocs) (void)hipFree(p);
     delete env;
 }

@@ -31,7 +31,7 @@ HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_op
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
                                    os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "measure.h"),
                                    os.path.join(CSRC, "fear_alt_tasks.h"), os.path.join(CSRC, "dispatch.h"),
-                                   os.path.join(CSRC, "obs_value.h")]
+                                   os.path.join(CSRC, "obs_value.h"), os.path.join(CSRC, "obs_dest.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -41,6 +41,7 @@ HIPCC_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-shared"
 COMPILE_FLAGS = [f for f in HIPCC_FLAGS if f != "-shared"]
 
 GW_MAX_AGENTS = 8
+GW_OBS_DESTS = 8  # include/gridenv.h: obs destinations the delta writer's table holds
 _lock = threading.Lock()
 _lib = None
 
@@ -189,7 +190,8 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_adam_soft_step", "gw_obs_desc_copy", "gw_replay_gather_desc",
            "gw_maddpg_desc_workspace_floats", "gw_maddpg_desc_prime", "gw_maddpg_desc_update", "gw_count_sims",
            "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
-           "gw_set_fear_alt", "gw_fear_regret_accum"]
+           "gw_set_fear_alt", "gw_fear_regret_accum",
+           "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts"]
 
 
 class GwObsSource(C.Structure):
@@ -398,6 +400,12 @@ def _declare(L):
     L.gw_fear_fence.restype = C.c_int
     L.gw_set_obs_dtype.argtypes = [p, C.c_int]
     L.gw_set_obs_dtype.restype = C.c_int
+    L.gw_set_obs_delta.argtypes = [p, C.c_int]
+    L.gw_set_obs_delta.restype = C.c_int
+    L.gw_obs_dest_forget.argtypes = [p, p]
+    L.gw_obs_dest_forget.restype = C.c_int
+    L.gw_obs_delta_counts.argtypes = [p, C.POINTER(C.c_int64)]
+    L.gw_obs_delta_counts.restype = C.c_int
     L.gw_set_fear_blocks.argtypes = [p, C.c_int]
     L.gw_set_fear_blocks.restype = C.c_int
     L.gw_destroy.argtypes = [p]

@@ -23,6 +23,7 @@ Layouts (device tensors, owned by the env and overwritten by the next call):
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 from dataclasses import dataclass
 
@@ -35,6 +36,13 @@ from .scenario import CompiledScenario, builtin
 
 @dataclass
 class StepResult:
+    """What a step returned (views of the env's buffers, or of the ``into`` destinations).
+
+    ``obs``: with the delta obs writer on (dense f32 obs; ``VecGridEnv.set_obs_delta``) the env
+    patches a buffer it wrote last in place instead of rewriting it.  Writes to that buffer through
+    torch ops are noticed (the tensor's version counter) and make the next step rewrite it in full;
+    a write torch cannot see (a kernel or library given the raw pointer) must be followed by
+    ``VecGridEnv.obs_dest_forget(buffer)`` before the env's next step into it."""
     obs: torch.Tensor
     reward: torch.Tensor
     fear: torch.Tensor
@@ -73,6 +81,11 @@ class StepGraph:
     def replay(self):
         self.graph.replay()
         self.env._replayed()
+
+
+# obs destination pointer -> uid of the VecGridEnv that stepped into it last (VecGridEnv._guard_dest)
+_DEST_WRITER: dict = {}
+_UIDS = itertools.count(1)
 
 
 def _ptr(t: torch.Tensor | None):
@@ -164,6 +177,16 @@ class VecGridEnv:
         self._dev_index = self.device.index
         self._closed = False
         self._obs_queued = False  # async obs: the last step's writer not yet launched / fenced
+        # the delta obs writer (gw_set_obs_delta): on for dense f32 obs; GW_OBS_DELTA=0 keeps it off
+        # (A/B; the results are the same).  _dest_guard: per obs destination the env wrote, what the
+        # library's promise rests on (see _guard_dest)
+        self._dest_guard = {}
+        self._queued_dest = None  # lazy async obs: the obs destination of the writer still queued
+        self._obs_lazy = False
+        self._uid = next(_UIDS)
+        self.obs_delta = False
+        if obs and obs_dtype == torch.float32 and os.environ.get("GW_OBS_DELTA", "1") != "0":
+            self.set_obs_delta(True)
         self.obs_async = False
         self.fear_async = False
         # the kernel path gw_create picked (GW_KERNEL, or by batch size: gw_kernel_path)
@@ -180,10 +203,12 @@ class VecGridEnv:
         spawn = self._as_i32(spawn, (self.E, self.N))
         if env_mask is not None:
             env_mask = env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        self._guard_queued()  # the reset launches a queued (lazy) writer first
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gw_reset(self.handle, _ptr(env_mask), _ptr(spawn), _ptr(self.out["obs"]),
                                          _ptr(self.out["mask"]), self._stream()), "gw_reset")
         self._obs_queued = False
+        self._queued_dest = None
         return self.out["obs"], self.out["mask"]
 
     _INTO_SPEC = {"obs": (torch.float32, "KEHW"), "final_obs": (torch.float32, "KEHW"),
@@ -223,6 +248,10 @@ class VecGridEnv:
                 self._into_cache.clear()
             self._into_cache[key] = cached
         so, res, result = cached
+        if self.obs_delta:
+            self._guard_queued()  # lazy async obs: this gw_step launches the previous step's writer first
+            if res["obs"] is not None:
+                self._guard_dest(res["obs"])
         if torch.cuda.current_device() != self._dev_index:
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.gw_step(self.handle, _ptr(rl), _ptr(sa), _ptr(sp), C.byref(so),
@@ -231,7 +260,74 @@ class VecGridEnv:
             _lib.check(self.lib.gw_step(self.handle, _ptr(rl), _ptr(sa), _ptr(sp), C.byref(so),
                                         torch.cuda.current_stream().cuda_stream), "gw_step")
         self._obs_queued = self.obs_async and (res["obs"] is not None or res["final_obs"] is not None)
+        self._queued_dest = res["obs"] if self._obs_queued and self._obs_lazy else None
         return result
+
+    def _guard_queued(self):
+        """Lazy async obs: the previous step's writer is still queued and is launched by the next
+        gw_step, fence or reset, so its destination is vetted again right before that (a torch write
+        since that step makes the queued writer a full one, as before the delta writer existed)."""
+        if self._queued_dest is not None and self.obs_delta:
+            self._guard_dest(self._queued_dest)
+
+    def _guard_dest(self, t: torch.Tensor):
+        """Keep the delta writer's promise (include/gridenv.h gw_set_obs_delta) for the obs
+        destination ``t`` of the step about to run: the library may patch the buffer in place only
+        if nothing but this env wrote it since the env's last step into it.  Per destination
+        pointer the guard holds the tensor (so the allocator cannot hand its address to another
+        tensor), its version counter (views share their base's: a ``copy_`` into any slot of a ring
+        invalidates the whole ring, which is conservative), its storage and its size; if any of them
+        differs now, the library forgets the destination first and this step rewrites it in full.
+        A destination never seen is unknown to the library anyway.  At most GW_OBS_DESTS
+        destinations are guarded; the least recently used is dropped (and forgotten by the library,
+        whose table evicts by the same rule)."""
+        ptr = t.data_ptr()
+        g = self._dest_guard.get(ptr)
+        if t.is_inference():  # no version counter to compare: never trusted
+            self.obs_dest_forget(ptr)
+            return
+        # the last VecGridEnv of this process that stepped into ptr: another env's write is invisible
+        # to torch's version counter too
+        mine = _DEST_WRITER.get(ptr) == self._uid
+        if not mine:
+            if len(_DEST_WRITER) >= 4096:
+                _DEST_WRITER.clear()  # every env then distrusts its destinations once
+            _DEST_WRITER[ptr] = self._uid
+        if g is not None:
+            if mine and t._version == g[1] and (g[0] is t or (t.untyped_storage()._cdata == g[2] and
+                                                              t.numel() == g[3])):
+                g[0] = t  # (possibly another view of the same bytes)
+                if len(self._dest_guard) >= _lib.GW_OBS_DESTS:  # full: keep the dict in order of use
+                    self._dest_guard[ptr] = self._dest_guard.pop(ptr)
+                return
+            self.obs_dest_forget(ptr)
+        elif len(self._dest_guard) >= _lib.GW_OBS_DESTS:
+            self.obs_dest_forget(next(iter(self._dest_guard)))
+        self._dest_guard[ptr] = [t, t._version, t.untyped_storage()._cdata, t.numel()]
+
+    def set_obs_delta(self, enable: bool = True):
+        """Turn the delta obs writer on / off (gw_set_obs_delta); either way every destination is
+        forgotten, so the next step into any buffer writes it in full."""
+        _lib.check(self.lib.gw_set_obs_delta(self.handle, int(bool(enable))), "gw_set_obs_delta")
+        self._dest_guard.clear()
+        self.obs_delta = bool(enable)
+
+    def obs_dest_forget(self, dest: torch.Tensor | int | None = None):
+        """Tell the env that something it cannot see wrote the obs buffer ``dest`` (a tensor or a
+        device pointer; None: every buffer) since the env's last step into it: a kernel given the
+        raw pointer, another library.  Writes through torch ops are seen by the env itself."""
+        ptr = dest.data_ptr() if isinstance(dest, torch.Tensor) else dest
+        _lib.check(self.lib.gw_obs_dest_forget(self.handle, ptr), "gw_obs_dest_forget")
+        if ptr is None:
+            self._dest_guard.clear()
+        else:
+            self._dest_guard.pop(ptr, None)
+
+    def obs_delta_counts(self):
+        """-> (full, delta): steps whose obs the full / the delta writer wrote (gw_obs_delta_counts)."""
+        out = (C.c_int64 * 2)()
+        _lib.check(self.lib.gw_obs_delta_counts(self.handle, out), "gw_obs_delta_counts")
+        return int(out[0]), int(out[1])
 
     def _build_into(self, over: dict):
         """(GwStepOut, result fields, StepResult) for the destination buffers ``over``."""
@@ -415,9 +511,12 @@ class VecGridEnv:
         mode = 2 if enable == "lazy" else int(bool(enable))
         if mode and fear_async:
             mode |= 4
+        self._guard_queued()  # switching the pipeline off launches a queued (lazy) writer
         _lib.check(self.lib.gw_set_obs_async(self.handle, mode), "gw_set_obs_async")
         if not mode:
             self._obs_queued = False
+            self._queued_dest = None
+        self._obs_lazy = bool(mode & 2)
         self.obs_async = bool(mode)
         self.fear_async = bool(mode & 4)
 
@@ -425,9 +524,11 @@ class VecGridEnv:
         """Order the last step's outputs (obs, and FeAR-owned ones) before later work on the
         current stream (async mode)."""
         if self.obs_async:
+            self._guard_queued()  # the fence launches a queued (lazy) writer
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.gw_obs_fence(self.handle, self._stream()), "gw_obs_fence")
             self._obs_queued = False
+            self._queued_dest = None
 
     def fear_fence(self):
         """Order the last step's FeAR-owned outputs before later work on the current stream."""
