@@ -160,7 +160,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * listing kernel, GW_SPAN_CNN_LIST their bucket scan + unit plan and scatter (two launches), GW_SPAN_CNN_RARE
  * their recompute of the listed conv positions, GW_SPAN_WINDOW the window writer (gw_obs_patch),
  * GW_SPAN_LEARN one whole descriptor-learner update (gw_maddpg_desc_update's four launches),
- * GW_SPAN_FEAR_ALT the per-action FeAR table's kernel (fear_alt_kernel, gw_set_fear_alt).
+ * GW_SPAN_FEAR_ALT the per-action FeAR table's kernel (fear_alt_kernel, gw_set_fear_alt),
+ * GW_SPAN_FEAL the per-agent FeAL kernel (feal_kernel, gw_set_feal).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -168,7 +169,7 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
 enum {
     GW_SPAN_STEP = 0, GW_SPAN_OBS = 1, GW_SPAN_FEAR = 2, GW_SPAN_ACT = 3, GW_SPAN_CNN_L1 = 4,
     GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8,
-    GW_SPAN_FEAR_ALT = 9
+    GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -257,6 +258,25 @@ gw_status gw_count_sims(void *env, uint64_t *counter);
  * too.  The pointer is kept in the env (not in gw_step_out), so captured steps replay it.  May be
  * called any time after gw_create; GW_ERR_ARG on a null env. */
 gw_status gw_set_fear_alt(void *env, double *fear_alt);
+
+/* Every following gw_step also writes, for every world agent i (all N, not only the K RL agents),
+ * Responsibility.FeAL (custom/Responsibility.py:213-303) of the step's pre-move world with the step's
+ * full joint action list and MdR4Agents (every agent listed) -- what gw_fear_matrix(in_list = NULL)
+ * gives for that snapshot:
+ *   feal [E][N] f64: clip(va / (vm + 1e-6), -1, 1), from a 10 x 10 table computed on the host at
+ *     gw_create (no division on the device);
+ *   feal_valid [E][N][2] u16: bit b of [..][0] / [..][1] = action b of agent i is valid (neither
+ *     crashed nor restricted) while every other agent plays its MdR / its actual action: the
+ *     reference's Validity_of_Moves_MdR_FeAL / _action_FeAL as bit sets; vm / va are their popcounts.
+ * Both NULL: off (the default); either alone may be NULL; feal_valid must be 4-byte aligned.  Both
+ * describe the pre-reset world of the step, as `fear`.  FeAR-owned outputs: ordered on the caller's
+ * stream like `fear`, with gw_set_obs_async(| 4) ready after gw_fear_fence.  One more kernel per step
+ * (feal_kernel: one wave per env, at most 18 N world updates), launched where fear_alt_kernel is;
+ * gw_count_sims counts its sims too.  The pointers are kept in the env, so captured steps replay them.
+ * FeAL is computed from the record the FeAR-on step kernels keep: on an env created with
+ * cfg.fear == 0 arming fails with GW_ERR_STATE (create the env with FeAR on, and fear_weight = 0 if
+ * the shaped reward must equal the env reward).  GW_ERR_ARG on a null env. */
+gw_status gw_set_feal(void *env, double *feal, uint16_t *feal_valid);
 
 /* Egocentric local patches of the env's last observation (an opt-in input format; the
  * reference observes the whole grid, ma_customenv.py:303-322): for every env and RL agent k the

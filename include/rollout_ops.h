@@ -131,6 +131,14 @@ gw_status gw_fear_row_accum(const double *fear_row, const uint8_t *active, int64
 gw_status gw_fear_regret_accum(const double *fear_alt, const double *fear, const uint8_t *active, int64_t E,
                                int32_t K, double *totals, int64_t *steps, void *stream);
 
+/* Per-agent FeAL totals of one step (gw_set_feal's feal, [E][N] f64):
+ * totals[i] += sum over e (active[e] != 0, or all if active == NULL) of feal[e][i];  *steps += 1;
+ * *envs += the number of those envs.  The lane groups, env order and fixed tree of
+ * gw_fear_row_accum: deterministic.  One block, graph-capturable, no host sync.  Call it before
+ * gw_eval_accum in an evaluation step. */
+gw_status gw_feal_accum(const double *feal, const uint8_t *active, int64_t E, int32_t N, double *totals,
+                        int64_t *steps, int64_t *envs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

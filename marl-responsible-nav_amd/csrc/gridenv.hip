@@ -38,6 +38,7 @@
 #include "philox.h"
 #include "window_rows.h"
 #include "fear_alt_tasks.h"
+#include "resp_tables.h"
 
 namespace gw {
 
@@ -102,7 +103,7 @@ struct Params {
     int obs_bf16;             // obs buffers hold bf16 (the merged step_obs kernel's writer role)
     int64_t e_begin, e_end;   // env range of this launch (step_v2 / obs_kernel chunks)
     uint4 *fwork;             // [E][FearRec<N>::R4] deferred-FeAR records (GW_KERNEL=defer; inline FeAR:
-                              // only while gw_set_fear_alt is armed, else null)
+                              // only while gw_set_fear_alt or gw_set_feal is armed, else null)
     int64_t stats_row0;       // first gw_step_out.stats row this launch writes
     int variant;              // 0 CustomMAEnv, 1 single-agent CustomEnv (custom/customenv.py)
     int apples[MAXN];
@@ -1680,7 +1681,7 @@ __device__ __forceinline__ void step_v2_block(const Params &p, int64_t bid, V2Sh
             fear_values<N, KMAX>(p, sh, tid, e, act, mdr, resp_s, fear);
             const uint32_t bits = sh.bits[tid];
             ObsInfo<N> oi;
-            // inline FeAR with the fear_alt table armed (uniform per launch): the record fear_alt_kernel reads
+            // inline FeAR with the fear_alt table or FeAL armed (uniform per launch): the record their kernels read
             finish_env<N>(p, e, es, act, mdr, fear, bits & 0xFFu, (bits >> 8) & 0xFFu, fin, bits >> 16, ct, oi, ctab,
                           p.fwork != nullptr);
             store_desc<N>(p, e, oi);
@@ -2036,6 +2037,97 @@ __global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__res
 }
 
 // ---------------------------------------------------------------------------------------
+// feal_kernel (gw_set_feal): Responsibility.FeAL (custom/Responsibility.py:213-303) of a step for
+// every world agent i, from the step's FearRec (pre-step cells, joint action; every agent listed):
+//   feal[e][i] = T[vm][va],  vm / va = agent i's valid moves (neither crashed nor restricted,
+//   CountValidMovesOfAffected :16-54) over its nine actions b while every other agent plays its
+//   MdR / its actual action; the two 9-bit sets go to valid[e][i][0 / 1].
+// The layout of fear_alt_kernel: one wave per env, FEAL_WAVES envs per block, the env's tasks dealt
+// to the wave's lanes round-robin, one register-resident world update per lane and turn.  Tasks
+// [0, 9 N): (i, others actual, b); then 9 per agent whose two variants differ: (i, others MdR, b).
+// The variants of i coincide when every other agent's action is its MdR (diff & ~(1 << i) == 0,
+// the same in every lane of the wave): that agent's MdR set is a copy of its actual set.
+// A task ORs bit b into the set (i, v) in LDS; after the barrier lane i counts and looks T up.
+// Dynamic LDS: [cell table][T 100 f64] (fear_lds' layout, T in the Resp table's place).
+// ---------------------------------------------------------------------------------------
+constexpr int FEAL_WAVES = 4, FEAL_T = 64 * FEAL_WAVES;
+
+template <int N>
+__global__ void __launch_bounds__(FEAL_T) feal_kernel(Params p, double *__restrict__ feal,
+                                                      uint16_t *__restrict__ valid_out) {
+    constexpr bool LIST = N >= GW_LIST_MIN_N;
+    constexpr int MAXT = 2 * NA * N;  // tasks per env at most
+    static_assert(MAXT <= 144, "18 N tasks per env: at most 3 turns of a wave");
+    __shared__ uint32_t vb[FEAL_WAVES][2 * N];  // [i][v]: 9-bit valid sets, v = 0 others MdR, 1 others actual
+    __shared__ uint2 wl[LIST ? FEAL_T * N : 1];  // World<N, true> rows (one per thread)
+    __shared__ unsigned int s_nsim;
+    static_assert(sizeof(uint32_t) * FEAL_WAVES * 2 * N + sizeof(uint2) * (LIST ? FEAL_T * N : 1) <= 17 * 1024,
+                  "static LDS of feal_kernel");
+    extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
+    uint32_t *ctab = reinterpret_cast<uint32_t *>(dyn + p.ctab_off);
+    double *tab_s = reinterpret_cast<double *>(dyn + p.resp_off);
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t e = p.e_begin + (int64_t)blockIdx.x * FEAL_WAVES + wave;
+    const bool live = e < p.e_end;  // uniform per wave
+    int pos[N], act[N], rew[MAXN];
+    uint32_t bonus = 0;
+    bool done = false;
+#pragma unroll
+    for (int n = 0; n < N; ++n) pos[n] = act[n] = 0;
+    if (live) load_fear_rec<N>(p, e, pos, act, rew, bonus, done);
+    lds_fill<FEAL_T>(ctab, p.tb.celltab, p.HW, tid);
+    lds_fill<FEAL_T>(reinterpret_cast<uint32_t *>(tab_s), reinterpret_cast<const uint32_t *>(p.tb.resp + 100), 200, tid);
+    if (lane < 2 * N) vb[wave][lane] = 0u;
+    if (tid == 0) s_nsim = 0u;
+    __syncthreads();
+    const CtabOk okv{ctab};
+
+    // the record's fields are clamped to their ranges before they index anything
+    int mdr[N];
+    uint32_t diff = 0u;  // agents whose action is not their MdR
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        pos[n] = min(pos[n], p.HW - 1);
+        act[n] = min(act[n], NA - 1);
+        mdr[n] = min((int)((ctab[pos[n]] >> CT_MDR) & 0xFu), NA - 1);
+        diff |= (uint32_t)(act[n] != mdr[n]) << n;
+    }
+    uint32_t need = 0u;  // agents whose others-MdR variant is a world of its own
+#pragma unroll
+    for (int i = 0; i < N; ++i) need |= (uint32_t)((diff & ~(1u << i)) != 0u) << i;
+    const int ntask = live ? NA * (N + __popc(need)) : 0;  // <= MAXT, from registers
+    if (lane == 0 && p.sims && ntask) atomicAdd(&s_nsim, (unsigned int)ntask);
+
+    for (int ti = lane; ti < min(ntask, MAXT); ti += 64) {
+        const int g = ti / NA, b = ti - g * NA;
+        const bool actual = g < N;
+        int i = actual ? g : fear_alt::nth_agent(need, g - N);
+        i = min(max(i, 0), N - 1);
+        int joint[N], fin[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) joint[n] = (n == i) ? b : (actual ? act[n] : mdr[n]);
+        int apple[MAXN];
+#pragma unroll
+        for (int q = 0; q < MAXN; ++q) apple[q] = -1;
+        World<N, LIST> w;
+        w.init(pos, joint, p.W, p.w_magic);
+        if constexpr (LIST) w.lw = &wl[tid * N];
+        uint32_t caught;
+        simulate<N, false>(w, okv, 0, apple, caught, fin);
+        if (!(((w.crash | w.restr) >> i) & 1u)) atomicOr(&vb[wave][2 * i + (actual ? 1 : 0)], 1u << b);
+    }
+    __syncthreads();
+    if (tid == 0 && p.sims && s_nsim) atomicAdd(p.sims, (unsigned long long)s_nsim);
+    if (!live || lane >= N) return;
+    const uint32_t va_set = vb[wave][2 * lane + 1] & 0x1FFu;
+    const uint32_t vm_set = ((need >> lane) & 1u) ? (vb[wave][2 * lane] & 0x1FFu) : va_set;
+    if (feal) feal[e * N + lane] = tab_s[__popc(vm_set) * 10 + __popc(va_set)];
+    // the pair [0] others MdR, [1] others actual as one 4-byte store (gw_set_feal checks the alignment)
+    if (valid_out) reinterpret_cast<uint32_t *>(valid_out)[e * N + lane] = vm_set | (va_set << 16);
+}
+
+// ---------------------------------------------------------------------------------------
 // Responsibility.FeAR (custom/Responsibility.py:57-132, every agent as actor) and FeAL
 // (:213-303) for n world snapshots, one 128-thread block per snapshot.  Every world update the
 // two need is one task (9 per group):  "act" groups jj = 0..N-1 (the action list unchanged,
@@ -2258,6 +2350,8 @@ struct Env {
     uint4 *fwork = nullptr;  // deferred-FeAR records (defer path with FeAR on)
     unsigned long long *sims = nullptr;  // gw_count_sims counter (device), or null
     double *fear_alt = nullptr;  // gw_set_fear_alt table [E][K][9] (caller's device buffer), or null
+    double *feal = nullptr;          // gw_set_feal: [E][N] f64 and [E][N][2] u16 (caller's device buffers), or null
+    uint16_t *feal_valid = nullptr;
     // gw_obs_patch's per-P tables of the map part of every window centre (patch_ops.hip MODE 4)
     std::vector<std::pair<int, float *>> ptbls;
     double *score = nullptr, *fscore = nullptr;
@@ -2281,6 +2375,9 @@ struct Env {
 
 // deferred FeAR: the world update stores FearRec records and fear_v2 runs as its own launch
 bool defer_fear(const Env *env) { return env->mode == PATH_DEFER && env->fear; }
+
+// gw_set_feal armed (FeAR on only: gw_set_feal refuses it otherwise)
+bool feal_armed(const Env *env) { return env->feal || env->feal_valid; }
 
 // n fork/join events (timing disabled), created on first use
 gw_status ensure_events(Env *env, int n) {
@@ -2432,8 +2529,8 @@ gw::Params make_params(const Env *env) {
     p.obs_bf16 = env->obs_bf16 ? 1 : 0;
     p.e_begin = 0;
     p.e_end = env->E;
-    // the step kernels store records on the defer path; with inline FeAR only for an armed fear_alt
-    p.fwork = defer_fear(env) || env->fear_alt ? env->fwork : nullptr;
+    // the step kernels store records on the defer path; with inline FeAR only for an armed fear_alt / FeAL
+    p.fwork = defer_fear(env) || env->fear_alt || feal_armed(env) ? env->fwork : nullptr;
     p.sims = env->sims;
     p.stats_row0 = 0;
     p.variant = env->variant;
@@ -2506,7 +2603,8 @@ int64_t ceil_div(int64_t n, int64_t d) { return (n + d - 1) / d; }
 // C2's step kernel slower: 11.4 -> 12.2 us, profiles/r3_c2.)
 size_t step_lds(const gw::Params &p, bool fear) { return (size_t)p.resp_off + (fear ? 100 * sizeof(double) : 0); }
 
-// dynamic LDS of the FeAR kernels (fear_v2, fear_rows_kernel, fear_alt_kernel): [cell table][Resp].
+// dynamic LDS of the FeAR kernels (fear_v2, fear_rows_kernel, fear_alt_kernel, feal_kernel):
+// [cell table][Resp] (feal_kernel: the FeAL table in Resp's place).
 // Sets p's offsets for it and returns its size.
 size_t fear_lds(gw::Params &p) {
     p.lds_cdf = 0;
@@ -2567,6 +2665,18 @@ hipError_t launch_fear_alt(const Env *env, const gw::Params &p0, hipStream_t s) 
     return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
         gw_launch((gw::fear_alt_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(count, gw::ALT_WAVES)),
                   dim3(gw::ALT_T), dyn, s, p, env->fear_alt);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_feal(const Env *env, const gw::Params &p0, hipStream_t s) {
+    gw::Params p = p0;
+    const size_t dyn = fear_lds(p);
+    const int64_t count = p.e_end - p.e_begin;
+    if (count <= 0) return hipSuccess;
+    return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
+        gw_launch((gw::feal_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(count, gw::FEAL_WAVES)),
+                  dim3(gw::FEAL_T), dyn, s, p, env->feal, env->feal_valid);
         return hipGetLastError();
     });
 }
@@ -2898,8 +3008,18 @@ gw_status step_fear_alt(Env *env, const gw::Params &p, hipStream_t s) {
     return GW_OK;
 }
 
+// gw_set_feal: the step's per-agent FeAL and valid-action sets, where the fear_alt table runs
+// (armed only with FeAR on: the world update stored the FearRec)
+gw_status step_feal(Env *env, const gw::Params &p, hipStream_t s) {
+    if (!feal_armed(env)) return GW_OK;
+    SpanGuard span(env, env->profiling, GW_SPAN_FEAL);
+    GW_TRY(span.status);
+    HIP_TRY(launch_feal(env, p, s));
+    return GW_OK;
+}
+
 // the FeAR stage of a step on s, behind its world update: fear_v2 on the defer path (elsewhere FeAR
-// ran inside the step kernel: nothing to launch), then the fear_alt table.  A step without obs
+// ran inside the step kernel: nothing to launch), then the fear_alt table and FeAL.  A step without obs
 // outputs whose armed window request (gw_step_patch_next) meets the row writer's conditions over
 // the whole env range writes the windows in the same launch (fear_rows_kernel).
 gw_status fear_stage(Env *env, const gw::Params &p, hipStream_t s) {
@@ -2920,7 +3040,8 @@ gw_status fear_stage(Env *env, const gw::Params &p, hipStream_t s) {
             HIP_TRY(launch_fear(env, p, s));
         }
     }
-    return step_fear_alt(env, p, s);
+    GW_TRY(step_fear_alt(env, p, s));
+    return step_feal(env, p, s);
 }
 
 // the step's obs writer on s as a GW_SPAN_OBS span (one per chunk)
@@ -3099,19 +3220,9 @@ gw_status gw_create(const gw_scenario *sc, const gw_config *cfg, int device, voi
         if (sc->apples[k] < 0 || sc->apples[k] >= HW) return fail(GW_ERR_ARG, "apple outside the grid");
     // Resp table: Responsibility.py:194-198 evaluated in IEEE f64 exactly as numpy does;
     // entries 100-199: FeAL = clip(va / (vm + EPS), -1, 1) (:282-285)
-    std::vector<double> resp(200);
-    for (int vm = 0; vm < 10; ++vm)
-        for (int va = 0; va < 10; ++va) {
-            volatile double num = (double)vm - (double)va;
-            volatile double den = (double)vm + 0.000001;
-            double r = num / den;
-            r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
-            resp[vm * 10 + va] = r;
-            volatile double fnum = (double)va;
-            double f = fnum / den;
-            f = f < -1.0 ? -1.0 : (f > 1.0 ? 1.0 : f);
-            resp[100 + vm * 10 + va] = f;
-        }
+    double resp_tab[200];
+    gwtab::fill(resp_tab);  // csrc/resp_tables.h
+    const std::vector<double> resp(resp_tab, resp_tab + 200);
 
     Env *env = new (std::nothrow) Env();
     if (!env) return fail(GW_ERR_ALLOC, "host allocation failed");
@@ -3463,6 +3574,25 @@ gw_status gw_set_fear_alt(void *handle, double *fear_alt) {
     // paths get them on first use (the step kernels store them only while the table is armed)
     if (fear_alt && env->fear && !env->fwork) GW_TRY(dalloc(env, &env->fwork, (size_t)env->E * (env->N <= 4 ? 1 : 2)));
     env->fear_alt = fear_alt;
+    return GW_OK;
+}
+
+gw_status gw_set_feal(void *handle, double *feal, uint16_t *feal_valid) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_set_feal: null env");
+    if (feal || feal_valid) {
+        // FeAL is computed from the step's FearRec, which only the FeAR-on step kernels store
+        if (!env->fear)
+            return fail(GW_ERR_STATE, "gw_set_feal: the env was created with FeAR off (cfg.fear == 0), so its steps keep "
+                                      "no record to compute FeAL from; create it with FeAR on (fear_weight = 0 if the "
+                                      "shaped reward must equal the env reward)");
+        if (reinterpret_cast<uintptr_t>(feal_valid) & 3u)
+            return fail(GW_ERR_ARG, "gw_set_feal: feal_valid not 4-byte aligned");
+        // as gw_set_fear_alt: the inline-FeAR paths get the record buffer on first use
+        if (!env->fwork) GW_TRY(dalloc(env, &env->fwork, (size_t)env->E * (env->N <= 4 ? 1 : 2)));
+    }
+    env->feal = feal;
+    env->feal_valid = feal_valid;
     return GW_OK;
 }
 

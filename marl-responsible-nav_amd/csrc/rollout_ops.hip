@@ -480,6 +480,45 @@ __global__ void __launch_bounds__(FR_T) fear_regret_accum_kernel(const double *_
     if (tid == 0 && steps) steps[0] += 1;
 }
 
+// ---- per-agent FeAL totals of one step (gw_set_feal's feal [E][N]): one block ----
+// F = N + 1 fields: field i < N sums feal[e][i], field N counts the summed envs (1.0 each: exact in
+// f64); the same lane groups, env order and tree as fear_row_accum_kernel
+__global__ void __launch_bounds__(FR_T) feal_accum_kernel(const double *__restrict__ feal,
+                                                          const uint8_t *__restrict__ active, int64_t E, int N,
+                                                          double *__restrict__ totals, int64_t *__restrict__ steps,
+                                                          int64_t *__restrict__ envs) {
+    __shared__ double part[FR_T];
+    const int nf = N + 1;
+    const int tid = threadIdx.x, groups = FR_T / nf, g = tid / nf, f = tid % nf;
+    double s = 0.0;
+    if (g < groups) {
+        for (int64_t e0 = g; e0 < E; e0 += (int64_t)FR_U * groups) {
+            double v[FR_U];
+#pragma unroll
+            for (int u = 0; u < FR_U; ++u) {
+                const int64_t e = e0 + (int64_t)u * groups;
+                v[u] = 0.0;
+                if (e < E && (!active || active[e])) v[u] = f < N ? feal[e * N + f] : 1.0;
+            }
+#pragma unroll
+            for (int u = 0; u < FR_U; ++u) s = __dadd_rn(s, v[u]);
+        }
+    }
+    part[tid] = s;
+    __syncthreads();
+    int pow2 = 1;
+    while (pow2 * 2 <= groups) pow2 *= 2;
+    if (g >= pow2 && g < groups) part[(g - pow2) * nf + f] = __dadd_rn(part[(g - pow2) * nf + f], s);
+    __syncthreads();
+    for (int stride = pow2 / 2; stride >= 1; stride /= 2) {
+        if (g < stride) part[g * nf + f] = __dadd_rn(part[g * nf + f], part[(g + stride) * nf + f]);
+        __syncthreads();
+    }
+    if (tid < N) totals[tid] = __dadd_rn(totals[tid], part[tid]);
+    if (tid == N && envs) envs[0] += (int64_t)part[N];
+    if (tid == 0 && steps) steps[0] += 1;
+}
+
 // ---- the packed per-step return gather (parallel.ReturnGather, world > 1) ----
 // Sender: this step's completed-episode returns (done envs, env order) are appended to a FIFO;
 // the send slot carries a 32-byte header {count, sent, backlog after, overflow} and the FIFO's
@@ -865,6 +904,22 @@ gw_status gw_fear_regret_accum(const double *fear_alt, const double *fear, const
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         gw_set_last_error((std::string("gw_fear_regret_accum: ") + hipGetErrorString(e)).c_str());
+        return GW_ERR_HIP;
+    }
+    return GW_OK;
+}
+
+gw_status gw_feal_accum(const double *feal, const uint8_t *active, int64_t E, int32_t N, double *totals,
+                        int64_t *steps, int64_t *envs, void *stream) {
+    if (!feal || !totals || !steps || !envs || E < 0 || N < 1 || N > GW_MAX_AGENTS) {
+        gw_set_last_error("gw_feal_accum: bad argument");
+        return GW_ERR_ARG;
+    }
+    hipLaunchKernelGGL(feal_accum_kernel, dim3(1), dim3(FR_T), 0, static_cast<hipStream_t>(stream), feal, active, E,
+                       (int)N, totals, steps, envs);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gw_set_last_error((std::string("gw_feal_accum: ") + hipGetErrorString(e)).c_str());
         return GW_ERR_HIP;
     }
     return GW_OK;

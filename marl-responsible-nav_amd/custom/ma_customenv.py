@@ -46,7 +46,9 @@ class CustomMAEnv:
     metadata = {"name": "custom_ma_env_hip"}
 
     def __init__(self, render=False, fear=True, seed=None, scenario: str | CompiledScenario = "level3",
-                 device=None):
+                 device=None, feal=False):
+        """feal (not in the reference's signature; needs fear=True): step()'s info dict also carries
+        info["feal"], Responsibility.FeAL of the step for every world agent (a length-N list)."""
         if render:
             raise NotImplementedError("render() is out of scope of the HIP build (pygame UI)")
         sc = builtin(scenario) if isinstance(scenario, str) else scenario
@@ -61,8 +63,11 @@ class CustomMAEnv:
                                     for a in self.possible_agents}
         self.rendering = False
         self.fear = fear
+        if feal and not fear:
+            raise ValueError("CustomMAEnv(feal=True) needs fear=True (FeAL is computed from the FeAR step's record)")
+        self.feal = bool(feal)
         self._env = VecGridEnv(sc, num_envs=1, fear=fear, fear_weight=0.0, max_steps=0, auto_reset=False,
-                               seed=self.seed, device=device, debug=True)
+                               seed=self.seed, device=device, debug=True, feal=self.feal)
         self._initialized = False
         self.Action4Agents = []
         self.MdR4Agents = []
@@ -144,6 +149,8 @@ class CustomMAEnv:
         info = {"fear": {a: np.float64(fear[k]) for k, a in enumerate(self.agents)},
                 "agent_crashes": int(r.crashes[0].item()),
                 "apples_caught": int(r.apples[0].item())}
+        if self.feal:
+            info["feal"] = r.feal[0].cpu().tolist()
         info.update(self._masks(r.mask[0].cpu().numpy()))
         return self.observations, self.rewards, self.terminations, self.truncation, info
 

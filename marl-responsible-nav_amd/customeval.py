@@ -25,6 +25,9 @@ def main(argv=None):
     ap.add_argument("--train-steps", type=int, default=150)
     ap.add_argument("--arch", default="mlp")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--feal", action="store_true",
+                    help="also print the mean FeAL (feasible action-space left) of every world agent; runs the "
+                         "env with FeAR on (the three totals do not depend on it)")
     args = ap.parse_args(argv)
 
     from marlnav import scenario as S
@@ -43,12 +46,14 @@ def main(argv=None):
         m = MADDPG(sc.K, sc.H, sc.W, arch=args.arch, device=torch.device("cuda"))
         m.load(args.checkpoint)
         actors = m.actors
-    r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps, fear=False, seed=args.seed,
-                 variant=variant)
+    r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps, fear=args.feal, seed=args.seed,
+                 variant=variant, feal=args.feal)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
     print(f"Total steps: {r['steps']} across {n} episodes")
+    if args.feal:
+        print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
 
 
 if __name__ == "__main__":

@@ -31,7 +31,8 @@ HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_op
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
                                    os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "measure.h"),
                                    os.path.join(CSRC, "fear_alt_tasks.h"), os.path.join(CSRC, "dispatch.h"),
-                                   os.path.join(CSRC, "obs_value.h"), os.path.join(CSRC, "obs_dest.h")]
+                                   os.path.join(CSRC, "obs_value.h"), os.path.join(CSRC, "obs_dest.h"),
+                                   os.path.join(CSRC, "resp_tables.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -191,7 +192,8 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_maddpg_desc_workspace_floats", "gw_maddpg_desc_prime", "gw_maddpg_desc_update", "gw_count_sims",
            "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
            "gw_set_fear_alt", "gw_fear_regret_accum",
-           "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts"]
+           "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts",
+           "gw_set_feal", "gw_feal_accum"]
 
 
 class GwObsSource(C.Structure):
@@ -343,6 +345,10 @@ def _declare(L):
     L.gw_set_fear_alt.restype = C.c_int
     L.gw_fear_regret_accum.argtypes = [p, p, p, C.c_int64, C.c_int32, p, p, p]
     L.gw_fear_regret_accum.restype = C.c_int
+    L.gw_set_feal.argtypes = [p, p, p]
+    L.gw_set_feal.restype = C.c_int
+    L.gw_feal_accum.argtypes = [p, p, C.c_int64, C.c_int32, p, p, p, p]
+    L.gw_feal_accum.restype = C.c_int
     L.gw_affine_relu_fwd.argtypes = [p, p, p, p, C.c_int32, C.c_int64, C.c_int32, p]
     L.gw_affine_relu_fwd.restype = C.c_int
     L.gw_affine_relu_bwd.argtypes = [p] * 7 + [C.c_int32, C.c_int64, C.c_int32, p]

@@ -180,7 +180,7 @@ class Rollout:
                  training: bool = True, group=None, seed: int = 0, fused: bool | None = None,
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
                  patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False,
-                 fear_regret: bool = False):
+                 fear_regret: bool = False, feal: bool = False):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -210,7 +210,11 @@ class Rollout:
         fear[e, k] - min_a fear_alt[e, k, a], and the count of envs whose agent k took a FeAR-minimal
         action are summed over the envs (gw_fear_regret_accum, one launch per step, also inside
         ``capture`` graphs); ``totals()`` then carries "fear_regret" [K], "fear_best" [K] and
-        "fear_regret_steps"."""
+        "fear_regret_steps".
+        feal (an env built with ``feal=True``): every step's per-agent FeAL (StepResult.feal) is summed
+        over the envs into a running [N] total (gw_feal_accum, one launch per step, also inside
+        ``capture`` graphs); ``totals()`` then carries "feal_sum" [N], "feal_envs" (the env-steps
+        summed, over all ranks) and "feal_steps"."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -281,6 +285,12 @@ class Rollout:
                 raise ValueError("Rollout(fear_regret=True) needs VecGridEnv(fear_alt=True)")
             self._regret = torch.zeros((env.K, 2), dtype=torch.float64, device=env.device)
             self._regret_steps = torch.zeros((), dtype=torch.int64, device=env.device)
+        self._feal = self._feal_cnt = None
+        if feal:
+            if env.out.get("feal") is None:
+                raise ValueError("Rollout(feal=True) needs VecGridEnv(feal=True)")
+            self._feal = torch.zeros(env.N, dtype=torch.float64, device=env.device)
+            self._feal_cnt = torch.zeros(2, dtype=torch.int64, device=env.device)  # steps, env-steps
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0
@@ -312,6 +322,12 @@ class Rollout:
                                                     self._regret_steps.data_ptr(),
                                                     torch.cuda.current_stream(env.device).cuda_stream),
                        "gw_fear_regret_accum")
+        if self._feal is not None:  # the step's per-agent FeAL (FeAR-owned as well)
+            env = self.env
+            cnt = self._feal_cnt.data_ptr()
+            _lib.check(env.lib.gw_feal_accum(env.out["feal"].data_ptr(), None, env.E, env.N, self._feal.data_ptr(),
+                                             cnt, cnt + 8, torch.cuda.current_stream(env.device).cuda_stream),
+                       "gw_feal_accum")
         if self.gather is not None:
             self.gather.push()  # the step wrote ep_return / done into the gather's send buffer
         if self._acc is not None:
@@ -580,9 +596,11 @@ class Rollout:
         (f64 CPU tensor), and "resp_steps", the steps it covers.
         With ``fear_regret``: "fear_regret" [K] (the summed hindsight FeAR regret), "fear_best" [K] (env-steps
         in which agent k's action was FeAR-minimal) and "fear_regret_steps".
+        With ``feal``: "feal_sum" [N] (every step's and env's FeAL per world agent, f64 CPU tensor),
+        "feal_envs" (the env-steps it sums: feal_sum / feal_envs is the mean FeAL) and "feal_steps".
         With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
         the responsibility total): every rank calls it."""
-        if self._acc is None and self._resp is None and self._regret is None:
+        if self._acc is None and self._resp is None and self._regret is None and self._feal is None:
             return {}
         self._flush()
         nst = _lib.GW_STATS if self._acc is not None else 0
@@ -591,6 +609,9 @@ class Rollout:
             parts.append(self._resp.reshape(-1))
         if self._regret is not None:
             parts.append(self._regret.reshape(-1))
+        if self._feal is not None:  # the env-step count rides along as a double (exact below 2^53)
+            parts.append(self._feal)
+            parts.append(self._feal_cnt[1:2].to(torch.float64))
         local = torch.cat(parts) if len(parts) > 1 else parts[0].clone()  # (the all-reduce is in place)
         if self.distributed:
             dist.all_reduce(local, group=self.group)
@@ -603,6 +624,12 @@ class Rollout:
             reg = local[nst:nst + 2 * self.env.K].reshape(self.env.K, 2).cpu()
             out["fear_regret"], out["fear_best"] = reg[:, 0].clone(), reg[:, 1].clone()
             out["fear_regret_steps"] = int(self._regret_steps)
+            nst += 2 * self.env.K
+        if self._feal is not None:
+            N = self.env.N
+            out["feal_sum"] = local[nst:nst + N].cpu()
+            out["feal_envs"] = int(local[nst + N])
+            out["feal_steps"] = int(self._feal_cnt[0])
         return out
 
     def completed_scores(self, last: int | None = None):

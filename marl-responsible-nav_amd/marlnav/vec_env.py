@@ -19,6 +19,13 @@ Layouts (device tensors, owned by the env and overwritten by the next call):
   fear_alt (fear_alt=True): [E, K, 9] float64, the step's FeAR of RL agent k had it played action a while
              everybody else did what they did (gw_set_fear_alt): fear_alt[e, k, actions[e, k]] is
              fear[e, k] and fear_alt[e, k, mdr[e, k]] is 0.0, bit for bit; zeros with FeAR off
+  feal (feal=True): [E, N] float64, Responsibility.FeAL of every world agent on the step's pre-move
+             world (gw_set_feal): how much of agent i's action space survived what the others did,
+             against what would have survived had they played their moves de rigueur
+  feal_valid (feal=True): [E, N, 2] int16 (views of the u16 bit sets, as mask): bit b of [..., 0] /
+             [..., 1] = action b of agent i is valid while the others play their MdR / their actual
+             actions; feal = clip(popcount([..., 1]) / (popcount([..., 0]) + 1e-6), -1, 1).
+             Needs fear=True (fear_weight=0.0 keeps shaped == reward)
 """
 from __future__ import annotations
 
@@ -69,6 +76,8 @@ class StepResult:
     desc_copy: torch.Tensor | None = None  # [E, 12] int32 copy of the obs descriptors (step(into=...))
     fear_row: torch.Tensor | None = None   # [E, K, N] per-pair responsibility rows (fear_rows=True)
     fear_alt: torch.Tensor | None = None   # [E, K, 9] per-action counterfactual FeAR (fear_alt=True)
+    feal: torch.Tensor | None = None       # [E, N] per-agent FeAL (feal=True)
+    feal_valid: torch.Tensor | None = None  # [E, N, 2] int16 valid-action bit sets: others MdR / actual (feal=True)
 
 
 class StepGraph:
@@ -101,7 +110,7 @@ class VecGridEnv:
                  device: torch.device | int | None = None, env_offset: int = 0, final_obs: bool = False,
                  debug: bool = False, obs: bool = True, stats: bool = False, variant: int | str = 0,
                  obs_dtype: torch.dtype = torch.float32, fear_rows: bool = False,
-                 fear_alt: bool = False):
+                 fear_alt: bool = False, feal: bool = False):
         if not torch.cuda.is_available():
             raise _lib.GwError("VecGridEnv needs a HIP device (no CPU fallback by design)")
         sc = builtin(scenario) if isinstance(scenario, str) else scenario
@@ -168,6 +177,9 @@ class VecGridEnv:
             fear_row=torch.zeros((E, K, N), **f64) if fear_rows else None,
             # not a gw_step_out field: the env keeps the pointer (gw_set_fear_alt), so it has no step(into=...)
             fear_alt=torch.zeros((E, K, 9), **f64) if fear_alt else None,
+            # the same (gw_set_feal)
+            feal=torch.zeros((E, N), **f64) if feal else None,
+            feal_valid=torch.zeros((E, N, 2), dtype=torch.int16, device=dev) if feal else None,
         )
         if fear_alt:
             _lib.check(self.lib.gw_set_fear_alt(self.handle, _ptr(self.out["fear_alt"])), "gw_set_fear_alt")
@@ -176,6 +188,12 @@ class VecGridEnv:
         self._into_sizes = None  # the destination sizes step(into=...) checks (built on first use)
         self._dev_index = self.device.index
         self._closed = False
+        if feal:
+            try:
+                self.set_feal(self.out["feal"], self.out["feal_valid"])
+            except _lib.GwError:  # FeAR off: no record to compute FeAL from
+                self.close()
+                raise
         self._obs_queued = False  # async obs: the last step's writer not yet launched / fenced
         # the delta obs writer (gw_set_obs_delta): on for dense f32 obs; GW_OBS_DELTA=0 keeps it off
         # (A/B; the results are the same).  _dest_guard: per obs destination the env wrote, what the
@@ -469,6 +487,18 @@ class VecGridEnv:
                        "gw_fear_matrix")
         return out
 
+    def set_feal(self, feal: torch.Tensor | None, feal_valid: torch.Tensor | None):
+        """Arm (or, with both None, disarm) the per-agent FeAL outputs of the following steps
+        (gw_set_feal): feal [E, N] float64, feal_valid [E, N, 2] int16; either may be None.  Raises
+        on an env created with fear=False (no FeAR record to compute FeAL from)."""
+        E, N = self.E, self.N
+        for t, dt, n in ((feal, torch.float64, E * N), (feal_valid, torch.int16, 2 * E * N)):
+            if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"set_feal: need a contiguous {dt} tensor of {n} elements on {self.device}")
+        _lib.check(self.lib.gw_set_feal(self.handle, _ptr(feal), _ptr(feal_valid)), "gw_set_feal")
+        self.out["feal"], self.out["feal_valid"] = feal, feal_valid
+        self._into_cache.clear()  # the cached StepResults carry the old views
+
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
         """Egocentric local observations (gw_obs_patch): [K, E, size, size] float32, agent k's obs
@@ -506,7 +536,7 @@ class VecGridEnv:
         enable="lazy": the writer is launched at the next step, behind the caller's work between
         the steps (an actor kernel), instead of right after the world update.
         fear_async (defer path, FeAR on): the FeAR-owned outputs (fear, shaped, ep_return,
-        ep_fear, fear_row, the FeAR stats rows) are ready only after ``fear_fence()``, so the caller's next
+        ep_fear, fear_row, fear_alt, feal, feal_valid, the FeAR stats rows) are ready only after ``fear_fence()``, so the caller's next
         work (the fused actor) overlaps the FeAR kernel."""
         mode = 2 if enable == "lazy" else int(bool(enable))
         if mode and fear_async:
