@@ -381,6 +381,25 @@ __device__ __forceinline__ void simulate(World<N, LIST> &w, const OK &okm, int K
     }
 }
 
+// One counterfactual world update of the wave-per-env kernels (fear_alt_kernel, feal_kernel): `pos`
+// under the joint action `joint`, no apples (APPLES is dead: K = 0).  Returns the N-bit set of agents
+// that end valid (neither crashed nor restricted).  LIST: wl_row is the lane's World::lw row.  fear_task
+// and fear_matrix_kernel keep this block in place (why: profiles/fear_scaffold/SUMMARY.md).
+template <int N, bool LIST, bool APPLES, class OK>
+__device__ __forceinline__ uint32_t cf_valid(int W, uint32_t w_magic, const OK &okv, const int (&pos)[N],
+                                             const int (&joint)[N], uint2 *wl_row) {
+    int fin[N];
+    int apple[MAXN];
+#pragma unroll
+    for (int q = 0; q < MAXN; ++q) apple[q] = -1;
+    World<N, LIST> w;
+    w.init(pos, joint, W, w_magic);
+    if constexpr (LIST) w.lw = wl_row;
+    uint32_t caught;
+    simulate<N, APPLES>(w, okv, 0, apple, caught, fin);
+    return ~(w.crash | w.restr) & ((1u << N) - 1u);
+}
+
 // numpy float64 sum (0.0 + pairwise_sum) of an N*N matrix whose only non-zero row is `row`
 // (np.sum(FeAR_vals), custom/ma_customenv.py:252).  Zeros never change a partial sum here
 // (no -0.0 can occur), so only the row's terms are accumulated, in numpy's order.
@@ -1443,6 +1462,7 @@ __device__ __forceinline__ void fear_task(const Params &p, Sh &sh, uint32_t tk, 
         if (n == k && var == 0) joint[n] = sh.mdr[el][n];
         if (n == j && b != 15) joint[n] = b;
     }
+    // cf_valid's block in place (profiles/fear_scaffold/SUMMARY.md)
     int apple[MAXN];
 #pragma unroll
     for (int q = 0; q < MAXN; ++q) apple[q] = -1;
@@ -1904,61 +1924,90 @@ __global__ void __launch_bounds__(128) fear_rows_kernel(Params p, PatchArgs a, u
 }
 
 // ---------------------------------------------------------------------------------------
+// CfEnv: the wave-per-env scaffold of fear_alt_kernel and feal_kernel.  Both run counterfactual
+// world updates from the step's FearRec (pre-step cells, joint action): one wave per env, CF_WAVES
+// envs per block, the env's tasks dealt to the wave's lanes round-robin, one register-resident world
+// update (cf_valid) per lane and turn.  A task ORs valid bits into the kernel's 9-bit sets in LDS
+// (`vb`), read after end()'s barrier.  Dynamic LDS (fear_lds): [cell table][100 f64 of p.tb.resp].
+// ---------------------------------------------------------------------------------------
+constexpr int CF_WAVES = 4, CF_T = 64 * CF_WAVES;
+
+template <int N>
+struct CfEnv {
+    int pos[N], act[N], mdr[N];  // the record's cells and joint action, the cells' MdR
+    int64_t e;
+    bool live;                   // e < p.e_end: uniform per wave (a wave past the range runs no task)
+    int wave, lane;
+    uint32_t *ctab;              // LDS: the cell table
+    double *tab;                 // LDS: the 100 f64 at p.tb.resp + tab_off
+
+    // Loads the env's record and fills the tables; zero_vb() clears the kernel's own sets before
+    // the block's first barrier.  s_nsim: the block's task count (a __shared__ word of the kernel).
+    template <class ZeroVb>
+    __device__ __forceinline__ void begin(const Params &p, int tab_off, unsigned int &s_nsim, ZeroVb zero_vb) {
+        extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
+        ctab = reinterpret_cast<uint32_t *>(dyn + p.ctab_off);
+        tab = reinterpret_cast<double *>(dyn + p.resp_off);
+        const int tid = threadIdx.x;
+        wave = tid >> 6, lane = tid & 63;
+        e = p.e_begin + (int64_t)blockIdx.x * CF_WAVES + wave;
+        live = e < p.e_end;
+        int rew[MAXN];
+        uint32_t bonus = 0;
+        bool done = false;
+#pragma unroll
+        for (int n = 0; n < N; ++n) pos[n] = act[n] = 0;
+        if (live) load_fear_rec<N>(p, e, pos, act, rew, bonus, done);
+        lds_fill<CF_T>(ctab, p.tb.celltab, p.HW, tid);
+        lds_fill<CF_T>(reinterpret_cast<uint32_t *>(tab), reinterpret_cast<const uint32_t *>(p.tb.resp + tab_off), 200, tid);
+        zero_vb();
+        if (tid == 0) s_nsim = 0u;
+        __syncthreads();
+        // the record's fields are clamped to their ranges before they index anything
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            pos[n] = min(pos[n], p.HW - 1);
+            act[n] = min(act[n], NA - 1);
+            mdr[n] = min((int)((ctab[pos[n]] >> CT_MDR) & 0xFu), NA - 1);
+        }
+    }
+
+    // The wave ran ntask world updates: the block's sum goes to p.sims (gw_count_sims) once.
+    __device__ __forceinline__ void end(const Params &p, unsigned int &s_nsim, int ntask) const {
+        if (lane == 0 && p.sims && ntask) atomicAdd(&s_nsim, (unsigned int)ntask);
+        __syncthreads();
+        if (threadIdx.x == 0 && p.sims && s_nsim) atomicAdd(p.sims, (unsigned long long)s_nsim);
+    }
+};
+
+// ---------------------------------------------------------------------------------------
 // fear_alt_kernel (gw_set_fear_alt): the per-action counterfactual FeAR table of a step,
 //   fear_alt[e][k][a] = np.sum(Resp) of FeAR_4_one_actor(actor = k) with k playing a,
-// from the step's FearRec (pre-step cells, joint action).  One wave per env, ALT_WAVES envs per
-// block; the env's tasks (csrc/fear_alt_tasks.h: per actor 9 variants x (1 base + 8 alternatives of
-// each close agent)) are dealt to the wave's lanes round-robin, one world update per lane and turn.
+// from the step's FearRec, on the wave-per-env scaffold (CfEnv).  The env's tasks are those of
+// csrc/fear_alt_tasks.h: per actor 9 variants x (1 base + 8 alternatives of each close agent).
 // A sim ORs the affected agent's valid bit into the 9-bit set vb[k][a][j] (bit b = j valid under
 // its action b; the base sim supplies bit act[j], and all nine bits of an agent outside the close
 // set, which stays: 9 * valid(base) as fear_values); popcounts give the V counts.  The MdR variant
 // is one of the nine, so Resp[k][j](a) = tab[V(mdr[k], j)][V(a, j)], summed by np_sum_row.
-// Dynamic LDS: [cell table][Resp 100 f64].
 // ---------------------------------------------------------------------------------------
-constexpr int ALT_WAVES = 4, ALT_T = 64 * ALT_WAVES;
-
 template <int N>
-__global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__restrict__ table) {
+__global__ void __launch_bounds__(CF_T) fear_alt_kernel(Params p, double *__restrict__ table) {
     constexpr bool LIST = N >= GW_LIST_MIN_N;
     constexpr int VBW = fear_alt::bit_words(N, N);  // per env, sized for K = N
     static_assert(fear_alt::max_per_env(4, 2) == 450 && fear_alt::max_per_env(8, 2) == 1026, "task maxima");
     static_assert(VBW == N * NA * N && VBW <= 576, "valid-bit sets: [K <= N][9][N] words per env");
     static_assert(fear_alt::max_per_env(N, N) <= 4104, "tasks per env fit an int with room");
-    __shared__ uint32_t vb[ALT_WAVES][VBW];
-    __shared__ uint2 wl[LIST ? ALT_T * N : 1];  // World<N, true> rows (one per thread)
+    __shared__ uint32_t vb[CF_WAVES][VBW];
+    __shared__ uint2 wl[LIST ? CF_T * N : 1];  // World<N, true> rows (one per thread)
     __shared__ unsigned int s_nsim;
-    static_assert(sizeof(uint32_t) * ALT_WAVES * VBW + sizeof(uint2) * (LIST ? ALT_T * N : 1) <= 26 * 1024,
+    static_assert(sizeof(uint32_t) * CF_WAVES * VBW + sizeof(uint2) * (LIST ? CF_T * N : 1) <= 26 * 1024,
                   "static LDS of fear_alt_kernel");
-    extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
-    uint32_t *ctab = reinterpret_cast<uint32_t *>(dyn + p.ctab_off);
-    double *resp_s = reinterpret_cast<double *>(dyn + p.resp_off);
-
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t e = p.e_begin + (int64_t)blockIdx.x * ALT_WAVES + wave;
-    const bool live = e < p.e_end;  // uniform per wave
-    const int K = min(p.K, N);
-    int pos[N], act[N], rew[MAXN];
-    uint32_t bonus = 0;
-    bool done = false;
-#pragma unroll
-    for (int n = 0; n < N; ++n) pos[n] = act[n] = 0;
-    if (live) load_fear_rec<N>(p, e, pos, act, rew, bonus, done);
-    lds_fill<ALT_T>(ctab, p.tb.celltab, p.HW, tid);
-    lds_fill<ALT_T>(reinterpret_cast<uint32_t *>(resp_s), reinterpret_cast<const uint32_t *>(p.tb.resp), 200, tid);
-    for (int i = lane; i < VBW; i += 64) vb[wave][i] = 0u;
-    if (tid == 0) s_nsim = 0u;
-    __syncthreads();
-    const CtabOk okv{ctab};
-
-    // the record's fields are clamped to their ranges before they index anything
-    int mdr[N];
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        pos[n] = min(pos[n], p.HW - 1);
-        act[n] = min(act[n], NA - 1);
-        mdr[n] = min((int)((ctab[pos[n]] >> CT_MDR) & 0xFu), NA - 1);
-    }
-    // close sets (ma_customenv.py:456-464) and task counts of the actors, in registers
+    CfEnv<N> c;
+    c.begin(p, 0, s_nsim, [&] { for (int i = c.lane; i < VBW; i += 64) vb[c.wave][i] = 0u; });
+    const int (&pos)[N] = c.pos, (&act)[N] = c.act, (&mdr)[N] = c.mdr;
+    const int tid = threadIdx.x, wave = c.wave, lane = c.lane, K = min(p.K, N);
+    const CtabOk okv{c.ctab};
+    // close sets and task counts of the actors, in registers
     uint32_t close[N];
     int tcount[N], ntask = 0;
 #pragma unroll
@@ -1972,8 +2021,7 @@ __global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__res
         tcount[k] = fear_alt::per_actor(__popc(close[k]));  // popc in 1..N: at most 9 (1 + 8 (N - 1))
         ntask += tcount[k];
     }
-    if (!live) ntask = 0;
-    if (lane == 0 && p.sims && ntask) atomicAdd(&s_nsim, (unsigned int)ntask);
+    if (!c.live) ntask = 0;
 
     for (int ti = lane; ti < ntask; ti += 64) {
         // (actor k, task r of k): the actors' tasks follow each other
@@ -1990,22 +2038,14 @@ __global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__res
             if (q == k) cl = close[q];
         const fear_alt::Task tk = fear_alt::decode(r, __popc(cl));
         const int j = tk.slot < 0 ? -1 : fear_alt::nth_agent(cl & ~(1u << k), tk.slot);
-        int joint[N], fin[N], b = 0;
+        int joint[N], b = 0;
 #pragma unroll
         for (int n = 0; n < N; ++n) {
             joint[n] = ((cl >> n) & 1u) ? act[n] : 0;
             if (n == k) joint[n] = tk.a;
             if (n == j) joint[n] = b = fear_alt::alternative(tk.bi, act[n]);
         }
-        int apple[MAXN];
-#pragma unroll
-        for (int q = 0; q < MAXN; ++q) apple[q] = -1;
-        World<N, LIST> w;
-        w.init(pos, joint, p.W, p.w_magic);
-        if constexpr (LIST) w.lw = &wl[tid * N];
-        uint32_t caught;
-        simulate<N, true>(w, okv, 0, apple, caught, fin);
-        const uint32_t valid = ~(w.crash | w.restr) & ((1u << N) - 1u);
+        const uint32_t valid = cf_valid<N, LIST, true>(p.W, p.w_magic, okv, pos, joint, LIST ? &wl[tid * N] : nullptr);
         uint32_t *row = &vb[wave][(k * NA + tk.a) * N];
         if (j >= 0) {
             if ((valid >> j) & 1u) atomicOr(&row[j], 1u << b);
@@ -2015,9 +2055,8 @@ __global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__res
                 if (n != k && ((valid >> n) & 1u)) atomicOr(&row[n], ((cl >> n) & 1u) ? (1u << act[n]) : 0x1FFu);
         }
     }
-    __syncthreads();
-    if (tid == 0 && p.sims && s_nsim) atomicAdd(p.sims, (unsigned long long)s_nsim);
-    if (!live) return;
+    c.end(p, s_nsim, ntask);
+    if (!c.live) return;
     // (k, a) per lane: V counts -> Resp table -> np.sum of the row in numpy's order
     for (int i = lane; i < K * NA; i += 64) {
         const int k = i / NA, a = i - k * NA;
@@ -2030,9 +2069,9 @@ __global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__res
 #pragma unroll
         for (int jj = 0; jj < N; ++jj) {
             const int vm = __popc(rm[jj] & 0x1FFu), va = __popc(ra[jj] & 0x1FFu);
-            resp[jj] = (jj == k) ? 0.0 : resp_s[vm * 10 + va];
+            resp[jj] = (jj == k) ? 0.0 : c.tab[vm * 10 + va];
         }
-        table[(e * p.K + k) * NA + a] = np_sum_row<N>(resp, k);
+        table[(c.e * p.K + k) * NA + a] = np_sum_row<N>(resp, k);
     }
 }
 
@@ -2042,89 +2081,54 @@ __global__ void __launch_bounds__(ALT_T) fear_alt_kernel(Params p, double *__res
 //   feal[e][i] = T[vm][va],  vm / va = agent i's valid moves (neither crashed nor restricted,
 //   CountValidMovesOfAffected :16-54) over its nine actions b while every other agent plays its
 //   MdR / its actual action; the two 9-bit sets go to valid[e][i][0 / 1].
-// The layout of fear_alt_kernel: one wave per env, FEAL_WAVES envs per block, the env's tasks dealt
-// to the wave's lanes round-robin, one register-resident world update per lane and turn.  Tasks
+// On the wave-per-env scaffold (CfEnv), with the FeAL table T in the Resp table's place.  Tasks
 // [0, 9 N): (i, others actual, b); then 9 per agent whose two variants differ: (i, others MdR, b).
 // The variants of i coincide when every other agent's action is its MdR (diff & ~(1 << i) == 0,
 // the same in every lane of the wave): that agent's MdR set is a copy of its actual set.
 // A task ORs bit b into the set (i, v) in LDS; after the barrier lane i counts and looks T up.
-// Dynamic LDS: [cell table][T 100 f64] (fear_lds' layout, T in the Resp table's place).
 // ---------------------------------------------------------------------------------------
-constexpr int FEAL_WAVES = 4, FEAL_T = 64 * FEAL_WAVES;
-
 template <int N>
-__global__ void __launch_bounds__(FEAL_T) feal_kernel(Params p, double *__restrict__ feal,
-                                                      uint16_t *__restrict__ valid_out) {
+__global__ void __launch_bounds__(CF_T) feal_kernel(Params p, double *__restrict__ feal,
+                                                    uint16_t *__restrict__ valid_out) {
     constexpr bool LIST = N >= GW_LIST_MIN_N;
     constexpr int MAXT = 2 * NA * N;  // tasks per env at most
     static_assert(MAXT <= 144, "18 N tasks per env: at most 3 turns of a wave");
-    __shared__ uint32_t vb[FEAL_WAVES][2 * N];  // [i][v]: 9-bit valid sets, v = 0 others MdR, 1 others actual
-    __shared__ uint2 wl[LIST ? FEAL_T * N : 1];  // World<N, true> rows (one per thread)
+    __shared__ uint32_t vb[CF_WAVES][2 * N];  // [i][v]: 9-bit valid sets, v = 0 others MdR, 1 others actual
+    __shared__ uint2 wl[LIST ? CF_T * N : 1];  // World<N, true> rows (one per thread)
     __shared__ unsigned int s_nsim;
-    static_assert(sizeof(uint32_t) * FEAL_WAVES * 2 * N + sizeof(uint2) * (LIST ? FEAL_T * N : 1) <= 17 * 1024,
+    static_assert(sizeof(uint32_t) * CF_WAVES * 2 * N + sizeof(uint2) * (LIST ? CF_T * N : 1) <= 17 * 1024,
                   "static LDS of feal_kernel");
-    extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
-    uint32_t *ctab = reinterpret_cast<uint32_t *>(dyn + p.ctab_off);
-    double *tab_s = reinterpret_cast<double *>(dyn + p.resp_off);
-
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t e = p.e_begin + (int64_t)blockIdx.x * FEAL_WAVES + wave;
-    const bool live = e < p.e_end;  // uniform per wave
-    int pos[N], act[N], rew[MAXN];
-    uint32_t bonus = 0;
-    bool done = false;
-#pragma unroll
-    for (int n = 0; n < N; ++n) pos[n] = act[n] = 0;
-    if (live) load_fear_rec<N>(p, e, pos, act, rew, bonus, done);
-    lds_fill<FEAL_T>(ctab, p.tb.celltab, p.HW, tid);
-    lds_fill<FEAL_T>(reinterpret_cast<uint32_t *>(tab_s), reinterpret_cast<const uint32_t *>(p.tb.resp + 100), 200, tid);
-    if (lane < 2 * N) vb[wave][lane] = 0u;
-    if (tid == 0) s_nsim = 0u;
-    __syncthreads();
-    const CtabOk okv{ctab};
-
-    // the record's fields are clamped to their ranges before they index anything
-    int mdr[N];
+    CfEnv<N> c;
+    c.begin(p, 100, s_nsim, [&] { if (c.lane < 2 * N) vb[c.wave][c.lane] = 0u; });
+    const int (&pos)[N] = c.pos, (&act)[N] = c.act, (&mdr)[N] = c.mdr;
+    const int tid = threadIdx.x, wave = c.wave, lane = c.lane;
+    const CtabOk okv{c.ctab};
     uint32_t diff = 0u;  // agents whose action is not their MdR
 #pragma unroll
-    for (int n = 0; n < N; ++n) {
-        pos[n] = min(pos[n], p.HW - 1);
-        act[n] = min(act[n], NA - 1);
-        mdr[n] = min((int)((ctab[pos[n]] >> CT_MDR) & 0xFu), NA - 1);
-        diff |= (uint32_t)(act[n] != mdr[n]) << n;
-    }
+    for (int n = 0; n < N; ++n) diff |= (uint32_t)(act[n] != mdr[n]) << n;
     uint32_t need = 0u;  // agents whose others-MdR variant is a world of its own
 #pragma unroll
     for (int i = 0; i < N; ++i) need |= (uint32_t)((diff & ~(1u << i)) != 0u) << i;
-    const int ntask = live ? NA * (N + __popc(need)) : 0;  // <= MAXT, from registers
-    if (lane == 0 && p.sims && ntask) atomicAdd(&s_nsim, (unsigned int)ntask);
+    const int ntask = c.live ? NA * (N + __popc(need)) : 0;  // <= MAXT, from registers
 
     for (int ti = lane; ti < min(ntask, MAXT); ti += 64) {
         const int g = ti / NA, b = ti - g * NA;
         const bool actual = g < N;
         int i = actual ? g : fear_alt::nth_agent(need, g - N);
         i = min(max(i, 0), N - 1);
-        int joint[N], fin[N];
+        int joint[N];
 #pragma unroll
         for (int n = 0; n < N; ++n) joint[n] = (n == i) ? b : (actual ? act[n] : mdr[n]);
-        int apple[MAXN];
-#pragma unroll
-        for (int q = 0; q < MAXN; ++q) apple[q] = -1;
-        World<N, LIST> w;
-        w.init(pos, joint, p.W, p.w_magic);
-        if constexpr (LIST) w.lw = &wl[tid * N];
-        uint32_t caught;
-        simulate<N, false>(w, okv, 0, apple, caught, fin);
-        if (!(((w.crash | w.restr) >> i) & 1u)) atomicOr(&vb[wave][2 * i + (actual ? 1 : 0)], 1u << b);
+        const uint32_t valid = cf_valid<N, LIST, false>(p.W, p.w_magic, okv, pos, joint, LIST ? &wl[tid * N] : nullptr);
+        if ((valid >> i) & 1u) atomicOr(&vb[wave][2 * i + (actual ? 1 : 0)], 1u << b);
     }
-    __syncthreads();
-    if (tid == 0 && p.sims && s_nsim) atomicAdd(p.sims, (unsigned long long)s_nsim);
-    if (!live || lane >= N) return;
+    c.end(p, s_nsim, ntask);
+    if (!c.live || lane >= N) return;
     const uint32_t va_set = vb[wave][2 * lane + 1] & 0x1FFu;
     const uint32_t vm_set = ((need >> lane) & 1u) ? (vb[wave][2 * lane] & 0x1FFu) : va_set;
-    if (feal) feal[e * N + lane] = tab_s[__popc(vm_set) * 10 + __popc(va_set)];
+    if (feal) feal[c.e * N + lane] = c.tab[__popc(vm_set) * 10 + __popc(va_set)];
     // the pair [0] others MdR, [1] others actual as one 4-byte store (gw_set_feal checks the alignment)
-    if (valid_out) reinterpret_cast<uint32_t *>(valid_out)[e * N + lane] = vm_set | (va_set << 16);
+    if (valid_out) reinterpret_cast<uint32_t *>(valid_out)[c.e * N + lane] = vm_set | (va_set << 16);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2203,6 +2207,7 @@ __global__ void __launch_bounds__(128) fear_matrix_kernel(FmParams q) {
 #pragma unroll
         for (int n = 0; n < N; ++n)
             if (n == affected && ((in >> n) & 1u)) joint[n] = b;
+        // cf_valid's block in place (profiles/fear_scaffold/SUMMARY.md)
         int apple[MAXN];
 #pragma unroll
         for (int k = 0; k < MAXN; ++k) apple[k] = -1;
@@ -2503,6 +2508,11 @@ gw_status dalloc(Env *env, T **ptr, size_t count) {
     return GW_OK;
 }
 
+// the FearRec buffer fear_alt_kernel and feal_kernel read: the inline-FeAR paths get it on first use
+gw_status ensure_fear_rec(Env *env) {
+    return env->fwork ? GW_OK : dalloc(env, &env->fwork, (size_t)env->E * (env->N <= 4 ? 1 : 2));
+}
+
 // ceil(2^32 / W): the kernels' division by W as a multiply
 uint32_t w_magic(int W) { return (uint32_t)((((uint64_t)1 << 32) + (uint64_t)W - 1) / (uint64_t)W); }
 
@@ -2657,28 +2667,22 @@ hipError_t launch_fear(const Env *env, const gw::Params &p0, hipStream_t s, cons
     });
 }
 
-hipError_t launch_fear_alt(const Env *env, const gw::Params &p0, hipStream_t s) {
+// a kernel on the wave-per-env scaffold (fear_alt_kernel, feal_kernel) over p's env range as one
+// span of `kind`: launch(n, grid, block, dyn, p) with n the env's agent count as a constant
+template <typename F>
+gw_status launch_cf(Env *env, int kind, const gw::Params &p0, F &&launch) {
     gw::Params p = p0;
     const size_t dyn = fear_lds(p);
     const int64_t count = p.e_end - p.e_begin;
-    if (count <= 0) return hipSuccess;
-    return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
-        gw_launch((gw::fear_alt_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(count, gw::ALT_WAVES)),
-                  dim3(gw::ALT_T), dyn, s, p, env->fear_alt);
+    SpanGuard span(env, env->profiling, kind);
+    GW_TRY(span.status);
+    if (count <= 0) return GW_OK;
+    const hipError_t launched = gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
+        launch(n, dim3((unsigned)ceil_div(count, gw::CF_WAVES)), dim3(gw::CF_T), dyn, p);
         return hipGetLastError();
     });
-}
-
-hipError_t launch_feal(const Env *env, const gw::Params &p0, hipStream_t s) {
-    gw::Params p = p0;
-    const size_t dyn = fear_lds(p);
-    const int64_t count = p.e_end - p.e_begin;
-    if (count <= 0) return hipSuccess;
-    return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
-        gw_launch((gw::feal_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(count, gw::FEAL_WAVES)),
-                  dim3(gw::FEAL_T), dyn, s, p, env->feal, env->feal_valid);
-        return hipGetLastError();
-    });
+    HIP_TRY(launched);
+    return GW_OK;
 }
 
 hipError_t launch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
@@ -3002,20 +3006,18 @@ gw_status step_fear_alt(Env *env, const gw::Params &p, hipStream_t s) {
         HIP_TRY(hipMemsetAsync(env->fear_alt, 0, sizeof(double) * (size_t)env->E * env->K * GW_N_ACTIONS, s));
         return GW_OK;
     }
-    SpanGuard span(env, env->profiling, GW_SPAN_FEAR_ALT);
-    GW_TRY(span.status);
-    HIP_TRY(launch_fear_alt(env, p, s));
-    return GW_OK;
+    return launch_cf(env, GW_SPAN_FEAR_ALT, p, [&](auto n, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        gw_launch((gw::fear_alt_kernel<decltype(n)::value>), grid, block, dyn, s, q, env->fear_alt);
+    });
 }
 
 // gw_set_feal: the step's per-agent FeAL and valid-action sets, where the fear_alt table runs
 // (armed only with FeAR on: the world update stored the FearRec)
 gw_status step_feal(Env *env, const gw::Params &p, hipStream_t s) {
     if (!feal_armed(env)) return GW_OK;
-    SpanGuard span(env, env->profiling, GW_SPAN_FEAL);
-    GW_TRY(span.status);
-    HIP_TRY(launch_feal(env, p, s));
-    return GW_OK;
+    return launch_cf(env, GW_SPAN_FEAL, p, [&](auto n, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        gw_launch((gw::feal_kernel<decltype(n)::value>), grid, block, dyn, s, q, env->feal, env->feal_valid);
+    });
 }
 
 // the FeAR stage of a step on s, behind its world update: fear_v2 on the defer path (elsewhere FeAR
@@ -3570,9 +3572,7 @@ gw_status gw_count_sims(void *handle, uint64_t *counter) {
 gw_status gw_set_fear_alt(void *handle, double *fear_alt) {
     Env *env = static_cast<Env *>(handle);
     if (!env) return fail(GW_ERR_ARG, "gw_set_fear_alt: null env");
-    // the kernel reads the step's FearRec: the defer path owns the records already, the inline-FeAR
-    // paths get them on first use (the step kernels store them only while the table is armed)
-    if (fear_alt && env->fear && !env->fwork) GW_TRY(dalloc(env, &env->fwork, (size_t)env->E * (env->N <= 4 ? 1 : 2)));
+    if (fear_alt && env->fear) GW_TRY(ensure_fear_rec(env));
     env->fear_alt = fear_alt;
     return GW_OK;
 }
@@ -3588,8 +3588,7 @@ gw_status gw_set_feal(void *handle, double *feal, uint16_t *feal_valid) {
                                       "shaped reward must equal the env reward)");
         if (reinterpret_cast<uintptr_t>(feal_valid) & 3u)
             return fail(GW_ERR_ARG, "gw_set_feal: feal_valid not 4-byte aligned");
-        // as gw_set_fear_alt: the inline-FeAR paths get the record buffer on first use
-        if (!env->fwork) GW_TRY(dalloc(env, &env->fwork, (size_t)env->E * (env->N <= 4 ? 1 : 2)));
+        GW_TRY(ensure_fear_rec(env));
     }
     env->feal = feal;
     env->feal_valid = feal_valid;

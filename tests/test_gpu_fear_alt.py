@@ -9,7 +9,8 @@
    whose MdR table is that constant (only the actor's MdR enters FeAR_4_one_actor).
 2. Native Philox rollouts on both kernel paths, auto-resets included: fear_alt[:, k, action] == fear,
    fear_alt[:, k, MdR] == 0 bit for bit every step, and a seeded sample of entries against
-   gw_fear_matrix on the pre-step cells with k's action replaced.
+   gw_fear_matrix on the pre-step cells with k's action replaced.  Built-ins (N = 4, 8) and level3
+   with N = 3 and N = 5 world agents.
 3. The table is result-neutral; NULL switches it off again.  4. FeAR off: zeros; the single-agent env.
 5. gw_fear_regret_accum against numpy.  6. Rollout(fear_regret=True) eager == graph replay; evaluate().
 
@@ -151,19 +152,33 @@ def test_reference_kats_through_fear_alt_kernel(group, path, monkeypatch):
     assert (want != 0).any()
 
 
+def _rollout_scenario(scen):
+    """A built-in, or "<built-in>@N": that built-in with N world agents (its map, policies and K)."""
+    name, _, n = scen.partition("@")
+    sc = S.builtin(name)
+    return dataclasses.replace(sc, name=f"{name}_n{n}", N=int(n)) if n else sc
+
+
+# level3@3: fewer agents than any built-in; level3@5: the first N of the kernels' LIST world update.
+# Their six steps end episodes through max_steps = 3; gw_fear_matrix, the comparison, is pinned at
+# N = 3 and N = 5 by the reference-recorded cases of tests/golden/fear_matrix.npz.
 @pytest.mark.parametrize("path", ["defer", "merged"])
-@pytest.mark.parametrize("scen,E", [("grid32", 256), ("grid64_n8", 64)])
-def test_native_rollout_identities_and_fear_matrix(scen, E, path, monkeypatch):
+@pytest.mark.parametrize("scen,E,steps,max_steps", [
+    pytest.param("grid32", 256, 20, 7, id="grid32-256"), pytest.param("grid64_n8", 64, 20, 7, id="grid64_n8-64"),
+    pytest.param("level3@3", 7, 6, 3, id="level3@3-7"), pytest.param("level3@5", 7, 6, 3, id="level3@5-7")])
+def test_native_rollout_identities_and_fear_matrix(scen, E, steps, max_steps, path, monkeypatch):
     _set_path(monkeypatch, path)
-    sc = S.builtin(scen)
+    sc = _rollout_scenario(scen)
     N, W, Kk = sc.N, sc.W, sc.K
-    env = VecGridEnv(sc, num_envs=E, fear=True, fear_weight=-5.0, seed=5, max_steps=7, debug=True, fear_alt=True)
+    env = VecGridEnv(sc, num_envs=E, fear=True, fear_weight=-5.0, seed=5, max_steps=max_steps, debug=True,
+                     fear_alt=True)
     assert env.kernel_path == KERNEL_PATHS[path]["GW_KERNEL"]
     env.reset()
+    assert tuple(env.positions().shape) == (E, N)
     rng = np.random.default_rng(17)
     ar = torch.arange(E, device=env.device)
     resets = nonzero = sampled = 0
-    for t in range(20):
+    for t in range(steps):
         cells = env.positions().cpu().numpy().astype(np.int64)  # pre-step (pre-reset) world
         env.out["fear_alt"].fill_(float("nan"))
         r = env.step()
@@ -190,7 +205,7 @@ def test_native_rollout_identities_and_fear_matrix(scen, E, path, monkeypatch):
             assert got[es[i], ks[i], as_[i]] == O.np_sum(m), (t, es[i], ks[i], as_[i])
         sampled += S_
     assert resets > 0, "no env auto-reset in the run"
-    assert nonzero > 0 and sampled == 480
+    assert nonzero > 0 and sampled == 24 * steps
     env.close()
 
 
