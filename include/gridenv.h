@@ -161,7 +161,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * their recompute of the listed conv positions, GW_SPAN_WINDOW the window writer (gw_obs_patch),
  * GW_SPAN_LEARN one whole descriptor-learner update (gw_maddpg_desc_update's four launches),
  * GW_SPAN_FEAR_ALT the per-action FeAR table's kernel (fear_alt_kernel, gw_set_fear_alt),
- * GW_SPAN_FEAL the per-agent FeAL kernel (feal_kernel, gw_set_feal).
+ * GW_SPAN_FEAL the per-agent FeAL kernel (feal_kernel, gw_set_feal),
+ * GW_SPAN_FEAR_FULL the N x N responsibility matrix's kernel (fear_full_kernel, gw_set_fear_full).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -169,7 +170,7 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
 enum {
     GW_SPAN_STEP = 0, GW_SPAN_OBS = 1, GW_SPAN_FEAR = 2, GW_SPAN_ACT = 3, GW_SPAN_CNN_L1 = 4,
     GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8,
-    GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10
+    GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -277,6 +278,24 @@ gw_status gw_set_fear_alt(void *env, double *fear_alt);
  * cfg.fear == 0 arming fails with GW_ERR_STATE (create the env with FeAR on, and fear_weight = 0 if
  * the shaped reward must equal the env reward).  GW_ERR_ARG on a null env. */
 gw_status gw_set_feal(void *env, double *feal, uint16_t *feal_valid);
+
+/* Every following gw_step also writes Responsibility.FeAR (custom/Responsibility.py:57-132) of the
+ * step's pre-move world with every world agent as actor (the scripted ones included) and every agent
+ * listed -- what gw_fear_matrix(in_list = NULL) gives for that snapshot, bit for bit:
+ *   resp_full [E][N][N] f64: resp_full[e][i][j] = clip((vm - va) / (vm + 1e-6), -1, 1), how much actor i
+ *     restricted agent j, from the 10 x 10 table computed on the host at gw_create; the diagonal is 0.0;
+ *   resp_valid [E][N][N][2] u16: bit b of [..][i][j][1] = action b of agent j is valid (neither crashed
+ *     nor restricted) with the step's action list unchanged except that j plays b, of [..][i][j][0] the
+ *     same with actor i swapped to its MdR: ValidMoves_action / _moveDeRigueur as bit sets, va / vm
+ *     their popcounts; the diagonal is zero.  [..][i][j][1] does not depend on i.
+ * Both NULL: off (the default); either alone may be NULL; resp_valid must be 4-byte aligned.  Rows of
+ * this matrix list every agent; gw_step_out.fear_row lists the step's close agents only, so the two
+ * agree where the close set is full.  Conventions of gw_set_feal: pre-reset world; FeAR-owned outputs
+ * ordered by gw_fear_fence; the pointers are kept in the env, so captured steps replay the writes;
+ * GW_ERR_STATE on an env created with cfg.fear == 0; GW_ERR_ARG on a null env.  One more kernel per step
+ * (fear_full_kernel: one wave per env, 9 N + 9 (N - 1) d <= 9 N^2 world updates with d the agents
+ * off their MdR), launched behind feal_kernel's place; gw_count_sims counts its sims too. */
+gw_status gw_set_fear_full(void *env, double *resp_full, uint16_t *resp_valid);
 
 /* Egocentric local patches of the env's last observation (an opt-in input format; the
  * reference observes the whole grid, ma_customenv.py:303-322): for every env and RL agent k the

@@ -25,5 +25,13 @@ inline void fill(double (&out)[200]) {
         }
 }
 
+// Resp(v, v) is exactly +0.0 for v = 0..9: fear_full_kernel (gw_set_fear_full) relies on it for the row
+// of an actor that plays its MdR
+inline bool resp_diag_zero(const double (&tab)[200]) {
+    for (int v = 0; v < 10; ++v)
+        if (tab[v * 10 + v] != 0.0 || 1.0 / tab[v * 10 + v] < 0.0) return false;
+    return true;
+}
+
 }  // namespace gwtab
 #endif  // RESP_TABLES_H

@@ -46,9 +46,11 @@ class CustomMAEnv:
     metadata = {"name": "custom_ma_env_hip"}
 
     def __init__(self, render=False, fear=True, seed=None, scenario: str | CompiledScenario = "level3",
-                 device=None, feal=False):
+                 device=None, feal=False, fear_full=False):
         """feal (not in the reference's signature; needs fear=True): step()'s info dict also carries
-        info["feal"], Responsibility.FeAL of the step for every world agent (a length-N list)."""
+        info["feal"], Responsibility.FeAL of the step for every world agent (a length-N list).
+        fear_full (likewise): info["fear_matrix"], Responsibility.FeAR of the step with every world agent
+        as actor and every agent listed (an N x N list of lists: actor i -> agent j)."""
         if render:
             raise NotImplementedError("render() is out of scope of the HIP build (pygame UI)")
         sc = builtin(scenario) if isinstance(scenario, str) else scenario
@@ -66,8 +68,13 @@ class CustomMAEnv:
         if feal and not fear:
             raise ValueError("CustomMAEnv(feal=True) needs fear=True (FeAL is computed from the FeAR step's record)")
         self.feal = bool(feal)
+        if fear_full and not fear:
+            raise ValueError("CustomMAEnv(fear_full=True) needs fear=True (the matrix is computed from the FeAR "
+                             "step's record)")
+        self.fear_full = bool(fear_full)
         self._env = VecGridEnv(sc, num_envs=1, fear=fear, fear_weight=0.0, max_steps=0, auto_reset=False,
-                               seed=self.seed, device=device, debug=True, feal=self.feal)
+                               seed=self.seed, device=device, debug=True, feal=self.feal,
+                               fear_full=self.fear_full)
         self._initialized = False
         self.Action4Agents = []
         self.MdR4Agents = []
@@ -151,6 +158,8 @@ class CustomMAEnv:
                 "apples_caught": int(r.apples[0].item())}
         if self.feal:
             info["feal"] = r.feal[0].cpu().tolist()
+        if self.fear_full:
+            info["fear_matrix"] = r.resp_full[0].cpu().tolist()
         info.update(self._masks(r.mask[0].cpu().numpy()))
         return self.observations, self.rewards, self.terminations, self.truncation, info
 

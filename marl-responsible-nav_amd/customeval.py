@@ -28,6 +28,9 @@ def main(argv=None):
     ap.add_argument("--feal", action="store_true",
                     help="also print the mean FeAL (feasible action-space left) of every world agent; runs the "
                          "env with FeAR on (the three totals do not depend on it)")
+    ap.add_argument("--resp-full", action="store_true",
+                    help="also print the N x N responsibility matrix (every world agent as actor, the scripted "
+                         "ones included) summed over the evaluation; runs the env with FeAR on")
     args = ap.parse_args(argv)
 
     from marlnav import scenario as S
@@ -46,14 +49,18 @@ def main(argv=None):
         m = MADDPG(sc.K, sc.H, sc.W, arch=args.arch, device=torch.device("cuda"))
         m.load(args.checkpoint)
         actors = m.actors
-    r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps, fear=args.feal, seed=args.seed,
-                 variant=variant, feal=args.feal)
+    r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps, fear=args.feal or args.resp_full,
+                 seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
     print(f"Total steps: {r['steps']} across {n} episodes")
     if args.feal:
         print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
+    if args.resp_full:
+        print(f"Responsibility matrix (actor i -> agent j) summed over {r['steps']} env-steps:")
+        for row in r["resp_full"].tolist():
+            print("  " + " ".join(f"{v:12.6f}" for v in row))
 
 
 if __name__ == "__main__":

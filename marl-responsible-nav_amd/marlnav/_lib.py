@@ -25,14 +25,15 @@ MEASURE = os.environ.get("MARLNAV_MEASURE", "0") == "1"
 LIB_PATH = os.path.join(CSRC, "libgridenv_measure.so" if MEASURE else "libgridenv.so")
 HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_ops.hip"),
                os.path.join(CSRC, "actor_ops.hip"), os.path.join(CSRC, "rollout_ops.hip"),
-               os.path.join(CSRC, "maddpg_ops.hip"), os.path.join(CSRC, "patch_ops.hip")]
+               os.path.join(CSRC, "maddpg_ops.hip"), os.path.join(CSRC, "patch_ops.hip"),
+               os.path.join(CSRC, "fear_full.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
                                    os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "measure.h"),
                                    os.path.join(CSRC, "fear_alt_tasks.h"), os.path.join(CSRC, "dispatch.h"),
                                    os.path.join(CSRC, "obs_value.h"), os.path.join(CSRC, "obs_dest.h"),
-                                   os.path.join(CSRC, "resp_tables.h")]
+                                   os.path.join(CSRC, "resp_tables.h"), os.path.join(CSRC, "cf_env.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -193,7 +194,7 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
            "gw_set_fear_alt", "gw_fear_regret_accum",
            "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts",
-           "gw_set_feal", "gw_feal_accum"]
+           "gw_set_feal", "gw_feal_accum", "gw_set_fear_full"]
 
 
 class GwObsSource(C.Structure):
@@ -349,6 +350,8 @@ def _declare(L):
     L.gw_set_feal.restype = C.c_int
     L.gw_feal_accum.argtypes = [p, p, C.c_int64, C.c_int32, p, p, p, p]
     L.gw_feal_accum.restype = C.c_int
+    L.gw_set_fear_full.argtypes = [p, p, p]
+    L.gw_set_fear_full.restype = C.c_int
     L.gw_affine_relu_fwd.argtypes = [p, p, p, p, C.c_int32, C.c_int64, C.c_int32, p]
     L.gw_affine_relu_fwd.restype = C.c_int
     L.gw_affine_relu_bwd.argtypes = [p] * 7 + [C.c_int32, C.c_int64, C.c_int32, p]

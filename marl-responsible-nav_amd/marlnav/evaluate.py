@@ -30,7 +30,7 @@ from .vec_env import VecGridEnv
 def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, max_steps: int = 150,
              fear: bool = False, seed: int = 42, record_actions: bool = False, fused: bool | None = None,
              variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False,
-             feal: bool = False) -> dict:
+             feal: bool = False, resp_full: bool = False) -> dict:
     """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
     matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
     restricted agent j) summed over the episodes still running and divided by "steps".
@@ -39,17 +39,24 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
     actions) per active env-step, and "fear_best_frac" [K], how often agent k's action was
     FeAR-minimal (f64 CPU tensors).
     feal (with ``fear=True``): the result also carries "feal" [N], the mean Responsibility.FeAL of every
-    world agent (StepResult.feal) per active env-step (f64 CPU tensor)."""
+    world agent (StepResult.feal) per active env-step (f64 CPU tensor).
+    resp_full (with ``fear=True``): the result also carries "resp_full", the [N, N] sum of every step's
+    responsibility matrix with every world agent as actor (StepResult.resp_full: how much agent i, RL or
+    scripted, restricted agent j) over the episodes still running (f64 CPU tensor; divide by "steps" for
+    the mean per env-step), and "resp_full_steps", the batched steps it covers."""
     if fear_regret and not fear:
         raise ValueError("evaluate(fear_regret=True) needs fear=True")
     if feal and not fear:
         raise ValueError("evaluate(feal=True) needs fear=True")
+    if resp_full and not fear:
+        raise ValueError("evaluate(resp_full=True) needs fear=True")
     sc = builtin(scenario) if isinstance(scenario, str) else scenario
     if fused is None:
         fused = actors.fusable(SimpleNamespace(K=sc.K, H=sc.H, W=sc.W))
     # the fused actor reads the obs descriptors: no dense obs is written at all
     env = VecGridEnv(sc, num_envs=episodes, fear=fear, max_steps=max_steps, auto_reset=False, seed=seed,
-                     obs=not fused, variant=variant, fear_rows=resp_matrix, fear_alt=fear_regret, feal=feal)
+                     obs=not fused, variant=variant, fear_rows=resp_matrix, fear_alt=fear_regret, feal=feal,
+                     fear_full=resp_full)
     try:
         obs, mask = env.reset()
         dev = env.device
@@ -63,6 +70,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         regret_calls = torch.zeros((), dtype=torch.int64, device=dev)
         feal_sum = torch.zeros(env.N, dtype=torch.float64, device=dev) if feal else None
         feal_cnt = torch.zeros(2, dtype=torch.int64, device=dev)  # calls, env-steps
+        full = torch.zeros((env.N, env.N), dtype=torch.float64, device=dev) if resp_full else None
+        full_calls = torch.zeros((), dtype=torch.int64, device=dev)
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):
@@ -86,6 +95,10 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
                 _lib.check(lib.gw_feal_accum(r.feal.data_ptr(), active.data_ptr(), episodes, env.N, feal_sum.data_ptr(),
                                              feal_cnt.data_ptr(), feal_cnt.data_ptr() + 8,
                                              torch.cuda.current_stream(dev).cuda_stream), "gw_feal_accum")
+            if resp_full:  # the active envs' N x N matrices: the row fold with every agent an actor
+                _lib.check(lib.gw_fear_row_accum(r.resp_full.data_ptr(), active.data_ptr(), episodes, env.N, env.N,
+                                                 full.data_ptr(), full_calls.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "gw_fear_row_accum")
             # the active envs' crashes, apples, steps and FeAR summed, then the done ones retired
             _lib.check(lib.gw_eval_accum(r.crashes.data_ptr(), r.apples.data_ptr(), r.fear.data_ptr(),
                                          r.done.data_ptr(), active.data_ptr(), counts.data_ptr(), fear_sum.data_ptr(),
@@ -106,6 +119,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             out["fear_regret"], out["fear_best_frac"] = reg[:, 0].clone(), reg[:, 1].clone()
         if feal:
             out["feal"] = (feal_sum / max(c[2], 1)).cpu()
+        if resp_full:
+            out["resp_full"], out["resp_full_steps"] = full.cpu(), int(full_calls)
         if record_actions:
             # the early-stop check runs every 8 steps: keep the actions up to the first step after
             # which every episode had ended (the steps an env-at-a-time loop would have taken)

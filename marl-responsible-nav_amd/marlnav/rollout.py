@@ -180,7 +180,7 @@ class Rollout:
                  training: bool = True, group=None, seed: int = 0, fused: bool | None = None,
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
                  patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False,
-                 fear_regret: bool = False, feal: bool = False):
+                 fear_regret: bool = False, feal: bool = False, resp_full: bool = False):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -214,7 +214,11 @@ class Rollout:
         feal (an env built with ``feal=True``): every step's per-agent FeAL (StepResult.feal) is summed
         over the envs into a running [N] total (gw_feal_accum, one launch per step, also inside
         ``capture`` graphs); ``totals()`` then carries "feal_sum" [N], "feal_envs" (the env-steps
-        summed, over all ranks) and "feal_steps"."""
+        summed, over all ranks) and "feal_steps".
+        resp_full (an env built with ``fear_full=True``): every step's N x N responsibility matrix
+        (StepResult.resp_full, every world agent as actor) is summed over the envs into a running [N, N]
+        total (gw_fear_row_accum with K = N, one launch per step, also inside ``capture`` graphs);
+        ``totals()`` then carries "resp_full" and "resp_full_steps"."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -291,6 +295,12 @@ class Rollout:
                 raise ValueError("Rollout(feal=True) needs VecGridEnv(feal=True)")
             self._feal = torch.zeros(env.N, dtype=torch.float64, device=env.device)
             self._feal_cnt = torch.zeros(2, dtype=torch.int64, device=env.device)  # steps, env-steps
+        self._full = self._full_steps = None
+        if resp_full:
+            if env.out.get("resp_full") is None:
+                raise ValueError("Rollout(resp_full=True) needs VecGridEnv(fear_full=True)")
+            self._full = torch.zeros((env.N, env.N), dtype=torch.float64, device=env.device)
+            self._full_steps = torch.zeros((), dtype=torch.int64, device=env.device)
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0
@@ -328,6 +338,12 @@ class Rollout:
             _lib.check(env.lib.gw_feal_accum(env.out["feal"].data_ptr(), None, env.E, env.N, self._feal.data_ptr(),
                                              cnt, cnt + 8, torch.cuda.current_stream(env.device).cuda_stream),
                        "gw_feal_accum")
+        if self._full is not None:  # the step's N x N matrix (FeAR-owned): the row fold with every agent an actor
+            env = self.env
+            _lib.check(env.lib.gw_fear_row_accum(env.out["resp_full"].data_ptr(), None, env.E, env.N, env.N,
+                                                 self._full.data_ptr(), self._full_steps.data_ptr(),
+                                                 torch.cuda.current_stream(env.device).cuda_stream),
+                       "gw_fear_row_accum")
         if self.gather is not None:
             self.gather.push()  # the step wrote ep_return / done into the gather's send buffer
         if self._acc is not None:
@@ -598,9 +614,13 @@ class Rollout:
         in which agent k's action was FeAR-minimal) and "fear_regret_steps".
         With ``feal``: "feal_sum" [N] (every step's and env's FeAL per world agent, f64 CPU tensor),
         "feal_envs" (the env-steps it sums: feal_sum / feal_envs is the mean FeAL) and "feal_steps".
+        With ``resp_full``: "resp_full", the [N, N] sum of every step's and env's responsibility matrix
+        (f64 CPU tensor, all-reduced with the rest), and "resp_full_steps", this rank's steps (like
+        "resp_steps": the ranks step in lockstep, so the count is not summed over them).
         With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
         the responsibility total): every rank calls it."""
-        if self._acc is None and self._resp is None and self._regret is None and self._feal is None:
+        if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
+                and self._full is None):
             return {}
         self._flush()
         nst = _lib.GW_STATS if self._acc is not None else 0
@@ -612,6 +632,8 @@ class Rollout:
         if self._feal is not None:  # the env-step count rides along as a double (exact below 2^53)
             parts.append(self._feal)
             parts.append(self._feal_cnt[1:2].to(torch.float64))
+        if self._full is not None:
+            parts.append(self._full.reshape(-1))
         local = torch.cat(parts) if len(parts) > 1 else parts[0].clone()  # (the all-reduce is in place)
         if self.distributed:
             dist.all_reduce(local, group=self.group)
@@ -630,6 +652,11 @@ class Rollout:
             out["feal_sum"] = local[nst:nst + N].cpu()
             out["feal_envs"] = int(local[nst + N])
             out["feal_steps"] = int(self._feal_cnt[0])
+            nst += N + 1
+        if self._full is not None:
+            N = self.env.N
+            out["resp_full"] = local[nst:nst + N * N].reshape(N, N).cpu()
+            out["resp_full_steps"] = int(self._full_steps)
         return out
 
     def completed_scores(self, last: int | None = None):

@@ -26,6 +26,13 @@ Layouts (device tensors, owned by the env and overwritten by the next call):
              [..., 1] = action b of agent i is valid while the others play their MdR / their actual
              actions; feal = clip(popcount([..., 1]) / (popcount([..., 0]) + 1e-6), -1, 1).
              Needs fear=True (fear_weight=0.0 keeps shaped == reward)
+  resp_full (fear_full=True): [E, N, N] float64, Responsibility.FeAR of the step's pre-move world with
+             every world agent as actor and every agent listed (gw_set_fear_full): resp_full[e, i, j] is
+             how much actor i (RL or scripted) restricted agent j; the diagonal is 0.0
+  resp_valid (fear_full=True): [E, N, N, 2] int16 (views of the u16 bit sets): bit b of [..., i, j, 1] =
+             action b of agent j is valid with everybody else on their actual actions (the same for
+             every i), of [..., i, j, 0] the same with actor i on its MdR; zero on the diagonal;
+             resp_full = clip((vm - va) / (vm + 1e-6), -1, 1) of their popcounts.  Needs fear=True
 """
 from __future__ import annotations
 
@@ -78,6 +85,8 @@ class StepResult:
     fear_alt: torch.Tensor | None = None   # [E, K, 9] per-action counterfactual FeAR (fear_alt=True)
     feal: torch.Tensor | None = None       # [E, N] per-agent FeAL (feal=True)
     feal_valid: torch.Tensor | None = None  # [E, N, 2] int16 valid-action bit sets: others MdR / actual (feal=True)
+    resp_full: torch.Tensor | None = None   # [E, N, N] responsibility matrix, every agent as actor (fear_full=True)
+    resp_valid: torch.Tensor | None = None  # [E, N, N, 2] int16 valid-action bit sets: actor on MdR / actual
 
 
 class StepGraph:
@@ -110,7 +119,7 @@ class VecGridEnv:
                  device: torch.device | int | None = None, env_offset: int = 0, final_obs: bool = False,
                  debug: bool = False, obs: bool = True, stats: bool = False, variant: int | str = 0,
                  obs_dtype: torch.dtype = torch.float32, fear_rows: bool = False,
-                 fear_alt: bool = False, feal: bool = False):
+                 fear_alt: bool = False, feal: bool = False, fear_full: bool = False):
         if not torch.cuda.is_available():
             raise _lib.GwError("VecGridEnv needs a HIP device (no CPU fallback by design)")
         sc = builtin(scenario) if isinstance(scenario, str) else scenario
@@ -180,6 +189,9 @@ class VecGridEnv:
             # the same (gw_set_feal)
             feal=torch.zeros((E, N), **f64) if feal else None,
             feal_valid=torch.zeros((E, N, 2), dtype=torch.int16, device=dev) if feal else None,
+            # and (gw_set_fear_full)
+            resp_full=torch.zeros((E, N, N), **f64) if fear_full else None,
+            resp_valid=torch.zeros((E, N, N, 2), dtype=torch.int16, device=dev) if fear_full else None,
         )
         if fear_alt:
             _lib.check(self.lib.gw_set_fear_alt(self.handle, _ptr(self.out["fear_alt"])), "gw_set_fear_alt")
@@ -188,10 +200,13 @@ class VecGridEnv:
         self._into_sizes = None  # the destination sizes step(into=...) checks (built on first use)
         self._dev_index = self.device.index
         self._closed = False
-        if feal:
+        if feal or fear_full:
             try:
-                self.set_feal(self.out["feal"], self.out["feal_valid"])
-            except _lib.GwError:  # FeAR off: no record to compute FeAL from
+                if feal:
+                    self.set_feal(self.out["feal"], self.out["feal_valid"])
+                if fear_full:
+                    self.set_fear_full(self.out["resp_full"], self.out["resp_valid"])
+            except _lib.GwError:  # FeAR off: no record to compute them from
                 self.close()
                 raise
         self._obs_queued = False  # async obs: the last step's writer not yet launched / fenced
@@ -499,6 +514,18 @@ class VecGridEnv:
         self.out["feal"], self.out["feal_valid"] = feal, feal_valid
         self._into_cache.clear()  # the cached StepResults carry the old views
 
+    def set_fear_full(self, resp_full: torch.Tensor | None, resp_valid: torch.Tensor | None):
+        """Arm (or, with both None, disarm) the N x N responsibility matrix of the following steps
+        (gw_set_fear_full): resp_full [E, N, N] float64, resp_valid [E, N, N, 2] int16; either may be
+        None.  Raises on an env created with fear=False (no FeAR record to compute it from)."""
+        n = self.E * self.N * self.N
+        for t, dt, m in ((resp_full, torch.float64, n), (resp_valid, torch.int16, 2 * n)):
+            if t is not None and (t.dtype != dt or t.numel() != m or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"set_fear_full: need a contiguous {dt} tensor of {m} elements on {self.device}")
+        _lib.check(self.lib.gw_set_fear_full(self.handle, _ptr(resp_full), _ptr(resp_valid)), "gw_set_fear_full")
+        self.out["resp_full"], self.out["resp_valid"] = resp_full, resp_valid
+        self._into_cache.clear()  # the cached StepResults carry the old views
+
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
         """Egocentric local observations (gw_obs_patch): [K, E, size, size] float32, agent k's obs
@@ -536,7 +563,7 @@ class VecGridEnv:
         enable="lazy": the writer is launched at the next step, behind the caller's work between
         the steps (an actor kernel), instead of right after the world update.
         fear_async (defer path, FeAR on): the FeAR-owned outputs (fear, shaped, ep_return,
-        ep_fear, fear_row, fear_alt, feal, feal_valid, the FeAR stats rows) are ready only after ``fear_fence()``, so the caller's next
+        ep_fear, fear_row, fear_alt, feal, feal_valid, resp_full, resp_valid, the FeAR stats rows) are ready only after ``fear_fence()``, so the caller's next
         work (the fused actor) overlaps the FeAR kernel."""
         mode = 2 if enable == "lazy" else int(bool(enable))
         if mode and fear_async:
