@@ -162,7 +162,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * GW_SPAN_LEARN one whole descriptor-learner update (gw_maddpg_desc_update's four launches),
  * GW_SPAN_FEAR_ALT the per-action FeAR table's kernel (fear_alt_kernel, gw_set_fear_alt),
  * GW_SPAN_FEAL the per-agent FeAL kernel (feal_kernel, gw_set_feal),
- * GW_SPAN_FEAR_FULL the N x N responsibility matrix's kernel (fear_full_kernel, gw_set_fear_full).
+ * GW_SPAN_FEAR_FULL the N x N responsibility matrix's kernel (fear_full_kernel, gw_set_fear_full),
+ * GW_SPAN_FEAR_PREVIEW the two launches of gw_fear_preview (preview_rec_kernel, fear_alt_kernel).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -170,7 +171,7 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
 enum {
     GW_SPAN_STEP = 0, GW_SPAN_OBS = 1, GW_SPAN_FEAR = 2, GW_SPAN_ACT = 3, GW_SPAN_CNN_L1 = 4,
     GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8,
-    GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11
+    GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11, GW_SPAN_FEAR_PREVIEW = 12
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -296,6 +297,29 @@ gw_status gw_set_feal(void *env, double *feal, uint16_t *feal_valid);
  * (fear_full_kernel: one wave per env, 9 N + 9 (N - 1) d <= 9 N^2 world updates with d the agents
  * off their MdR), launched behind feal_kernel's place; gw_count_sims counts its sims too. */
 gw_status gw_set_fear_full(void *env, double *resp_full, uint16_t *resp_valid);
+
+/* The forward-looking twin of gw_set_fear_alt: the per-action FeAR table of the step that
+ * gw_step(env, rl_actions, scripted, ...) WOULD run next, without moving the world.
+ *   fear_alt [E][K][9] f64: what gw_set_fear_alt's table would hold after that gw_step, provided nothing
+ *     else touches the env in between, bit for bit (the same fear_alt_kernel, Resp table and numpy-ordered
+ *     sum): agent k's FeAR had it played action a on the current world while everybody else plays the
+ *     action the step will apply.  fear_alt[e][k][mdr[e][k]] == 0.0.
+ *   actions [E][N] i32 or NULL: the joint action that step will apply (gw_step_out.actions);
+ *   mdr [E][N] i32 or NULL: the current cells' MdR (gw_step_out.mdr).
+ * rl_actions [E][K] / scripted [E][N-K] as gw_step's; NULL: the device-random RL policy / the scenario
+ * policy, drawn with the Philox counters (seed; global env, episode, step, agent) the step itself uses,
+ * so the draws are the step's.  Works on an env created with cfg.fear == 0 too (it needs no record from a
+ * step kernel) and then gives the table of a FeAR-on twin with the same seed.
+ * It changes no env state, no step output, no pipeline state and no obs-destination table, and it does
+ * not touch the steps' record buffer: it keeps one of its own, [E] records, allocated by the first call
+ * (a first call while `stream` is capturing returns GW_ERR_STATE; later calls can be captured).  No host
+ * synchronisation: two launches enqueued on `stream` (preview_rec_kernel, one thread per env, then
+ * fear_alt_kernel), one GW_SPAN_FEAR_PREVIEW span while profiling; gw_count_sims counts the world updates.
+ * Every path of gw_step orders its world update before the caller's later work on the step's stream, so
+ * a preview enqueued there after a step sees that step's state (with gw_set_obs_async(| 4) as well).
+ * GW_ERR_STATE before the first gw_reset; GW_ERR_ARG on a null env or a null table. */
+gw_status gw_fear_preview(void *env, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,
+                          int32_t *actions, int32_t *mdr, void *stream);
 
 /* Egocentric local patches of the env's last observation (an opt-in input format; the
  * reference observes the whole grid, ma_customenv.py:303-322): for every env and RL agent k the

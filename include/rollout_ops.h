@@ -139,6 +139,27 @@ gw_status gw_fear_regret_accum(const double *fear_alt, const double *fear, const
 gw_status gw_feal_accum(const double *feal, const uint8_t *active, int64_t E, int32_t N, double *totals,
                         int64_t *steps, int64_t *envs, void *stream);
 
+/* The responsibility shield: replace an RL action whose previewed FeAR exceeds tau, before the world moves.
+ * fear_alt [E][K][9] f64 (gw_fear_preview's table for the proposed joint action), actions_in / actions_out
+ * [E][K] i32 (may be the same buffer), mask [E][K] u16 9-bit action masks (NULL: all nine), probs
+ * [K][E][9] f32 the actor's probabilities in the replay ring's layout (NULL: none), flags [E][K] u8 or
+ * NULL, agents: bit k set = agent k is shielded.  Per (e, k), proposed action p, row t, mask m
+ * (csrc/fear_shield.h, the same text the CPU check runs):
+ *   bit k of agents clear, or m == 0: keep p, flags 0;
+ *   A = { a : bit a of m set and t[a] <= tau } (f64 compare);  p in A: keep p, flags 0;
+ *   A non-empty: the a in A with the largest probs[k][e][a] (no probs: the smallest t[a]), ties to the
+ *     lowest a, flags 1 (replaced);
+ *   A empty: the masked a with the smallest t[a], ties to the lowest a, flags 2 (stuck), 3 if it is not p.
+ * t[mdr] == 0.0 always, so with tau >= 0 A is empty only when the mask forbids the MdR.
+ * The shield is UNILATERAL: every row assumes that the other agents play their proposed actions.  When
+ * one agent alone is shielded (agents = 1 << k), the following step's fear[e][k] is exactly the chosen
+ * entry t[actions_out[e][k]], hence <= tau wherever flag bit 1 is clear.  With several agents shielded
+ * at once that holds for an agent only in the envs where every other agent's action was kept.
+ * One launch, one thread per (env, agent), deterministic, graph-capturable, no host sync. */
+gw_status gw_fear_shield(const double *fear_alt, const int32_t *actions_in, const uint16_t *mask,
+                         const float *probs, int64_t E, int32_t K, double tau, uint32_t agents,
+                         int32_t *actions_out, uint8_t *flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -517,4 +517,9 @@ struct CfEnv {
 hipError_t launch_fear_full(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
                             double *resp_full, uint16_t *resp_valid);
 
+// preview_rec_kernel<N> (fear_preview.hip, gw_fear_preview) over p's env range on s, through gwprof::launch:
+// the record of the step the next gw_step will run into p.fwork, its joint action and MdRs into actions / mdr
+// ([E][N] or null)
+hipError_t launch_preview_rec(int N, hipStream_t s, const Params &p, int32_t *actions, int32_t *mdr);
+
 }  // namespace gw

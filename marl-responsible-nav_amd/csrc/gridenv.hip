@@ -921,33 +921,7 @@ struct alignas(16) V2Shared {
     int nbase, ngroup;  // base-sim entries after the env sims; counterfactual groups
 };
 
-// setup_step (ma_customenv.py:432-452) + RL override (:239-242) from the LDS tables: agent n
-__device__ __forceinline__ int draw_action(const Params &p, int64_t e, int n, uint32_t episode, int t, int pos,
-                                           const uint32_t *ctab, const double *cdf_s) {
-    const uint32_t gid = (uint32_t)(p.env_offset + e);
-    int a;
-    if (n < p.K) {
-        if (p.rl) {
-            a = p.rl[e * p.K + n];
-        } else {
-            const uint4 r = gwrng::philox(gid, episode, (uint32_t)t, (2u << 24) | (uint32_t)n, p.key0, p.key1);
-            a = (int)(((uint64_t)r.x * 9u) >> 32);
-        }
-    } else if (p.scripted) {
-        a = p.scripted[e * (p.N - p.K) + (n - p.K)];
-    } else {
-        const uint4 r = gwrng::philox(gid, episode, (uint32_t)t, (1u << 24) | (uint32_t)n, p.key0, p.key1);
-        const int uni = r.x < 0x40000000u;  // random.random() < 0.25 (:441)
-        const double u = ((double)(r.y >> 5) * 67108864.0 + (double)(r.z >> 6)) * (1.0 / 9007199254740992.0);
-        const int pid = (int)((ctab[pos] >> CT_POL) & 0xFFu);
-        const double *cdf = (cdf_s ? cdf_s : p.tb.cdf) + (pid * 2 + uni) * NA;
-        a = NA - 1;
-#pragma unroll
-        for (int q = NA - 2; q >= 0; --q)
-            if (u < cdf[q]) a = q;  // searchsorted(cdf, u, 'right')
-    }
-    return ((unsigned)a < (unsigned)NA) ? a : 0;
-}
+#include "draw_action.h"  // draw_action: one agent's action of the step (shared with fear_preview.hip)
 
 template <int N>
 __device__ __forceinline__ void select_actions_v2(const Params &p, int64_t e, const EnvState<N> &es,
@@ -1861,6 +1835,9 @@ struct Env {
     uint16_t *feal_valid = nullptr;
     double *resp_full = nullptr;     // gw_set_fear_full: [E][N][N] f64 and [E][N][N][2] u16 (caller's), or null
     uint16_t *resp_valid = nullptr;
+    // gw_fear_preview's own record buffer [E][FearRec<N>::R4] (first call): never the step's fwork, which a
+    // previous step's fear_alt / FeAL / full-matrix kernels may still be reading on the aux stream
+    uint4 *preview_rec = nullptr;
     // gw_obs_patch's per-P tables of the map part of every window centre (patch_ops.hip MODE 4)
     std::vector<std::pair<int, float *>> ptbls;
     double *score = nullptr, *fscore = nullptr;
@@ -3130,6 +3107,39 @@ gw_status gw_set_fear_full(void *handle, double *resp_full, uint16_t *resp_valid
     }
     env->resp_full = resp_full;
     env->resp_valid = resp_valid;
+    return GW_OK;
+}
+
+gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,
+                          int32_t *actions, int32_t *mdr, void *stream) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_fear_preview: null env");
+    if (!fear_alt) return fail(GW_ERR_ARG, "gw_fear_preview: null table");
+    if (!env->initialized) return fail(GW_ERR_STATE, "gw_fear_preview before gw_reset");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!env->preview_rec) {  // hipMalloc is not allowed while the stream captures
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone)
+            return fail(GW_ERR_STATE, "gw_fear_preview: the first call allocates the record buffer and cannot run "
+                                      "while the stream is capturing; call it once before the capture");
+        GW_TRY(dalloc(env, &env->preview_rec, (size_t)env->E * (env->N <= 4 ? 1 : 2)));
+    }
+    // the env's state as the next gw_step will read it: every path orders the last world update before the
+    // caller's later work on its stream.  No step output, no descriptor, no pipeline state is touched
+    gw::Params p = make_params(env);
+    p.rl = rl_actions;
+    p.scripted = scripted;
+    p.fwork = env->preview_rec;
+    hipError_t rec = hipSuccess;
+    GW_TRY(launch_cf(env, GW_SPAN_FEAR_PREVIEW, p, [&](auto n, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        // the record builder (fear_preview.hip, its own code object), then the step's own table kernel on that
+        // record: both launches are the one span
+        rec = gw::launch_preview_rec(env->N, s, q, actions, mdr);
+        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
+        gw_launch((gw::fear_alt_kernel<decltype(n)::value>), grid, block, dyn, s, q, fear_alt);
+    }));
+    HIP_TRY(rec);
     return GW_OK;
 }
 

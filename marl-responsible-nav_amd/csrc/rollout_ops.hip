@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <string>
 
+#include "fear_shield.h"
 #include "obs_value.h"
 #include "philox.h"
 #include "rollout_ops.h"
@@ -711,6 +712,26 @@ __global__ void __launch_bounds__(PT) unpack_copy(const uint8_t *__restrict__ re
     }
 }
 
+// ---- gw_fear_shield: one thread per (env, RL agent), the rule of csrc/fear_shield.h ----
+// Thread i = e K + k reads its proposed action before it stores the chosen one, so actions_out may be
+// actions_in; the table row [9] f64 and the probability row [9] f32 (ring layout [K][E][9]) are contiguous.
+constexpr int SH_T = 256;
+__global__ void __launch_bounds__(SH_T) fear_shield_kernel(const double *__restrict__ alt, const int32_t *actions_in,
+                                                           const uint16_t *__restrict__ mask,
+                                                           const float *__restrict__ probs, int64_t E, int K, double tau,
+                                                           uint32_t agents, int32_t *actions_out,
+                                                           uint8_t *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * SH_T + threadIdx.x;
+    if (i >= E * K) return;
+    const int64_t e = i / K;
+    const int k = (int)(i - e * K);
+    const uint32_t m = mask ? mask[i] : 0x1FFu;
+    const fear_shield::Pick r = fear_shield::pick(alt + i * 9, actions_in[i], m, probs ? probs + ((int64_t)k * E + e) * 9 : nullptr,
+                                                  tau, (agents >> k) & 1u);
+    actions_out[i] = r.action;
+    if (flags) flags[i] = (uint8_t)r.flags;
+}
+
 }  // namespace
 
 extern "C" {
@@ -920,6 +941,26 @@ gw_status gw_feal_accum(const double *feal, const uint8_t *active, int64_t E, in
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         gw_set_last_error((std::string("gw_feal_accum: ") + hipGetErrorString(e)).c_str());
+        return GW_ERR_HIP;
+    }
+    return GW_OK;
+}
+
+gw_status gw_fear_shield(const double *fear_alt, const int32_t *actions_in, const uint16_t *mask, const float *probs,
+                         int64_t E, int32_t K, double tau, uint32_t agents, int32_t *actions_out, uint8_t *flags,
+                         void *stream) {
+    if (!fear_alt || !actions_in || !actions_out || E < 0 || K < 1 || K > GW_MAX_AGENTS ||
+        E * K > (int64_t)0x7FFFFFFF * SH_T) {
+        gw_set_last_error("gw_fear_shield: bad argument");
+        return GW_ERR_ARG;
+    }
+    if (E == 0) return GW_OK;
+    hipLaunchKernelGGL(fear_shield_kernel, dim3((unsigned)((E * K + SH_T - 1) / SH_T)), dim3(SH_T), 0,
+                       static_cast<hipStream_t>(stream), fear_alt, actions_in, mask, probs, E, (int)K, tau, agents,
+                       actions_out, flags);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gw_set_last_error((std::string("gw_fear_shield: ") + hipGetErrorString(e)).c_str());
         return GW_ERR_HIP;
     }
     return GW_OK;

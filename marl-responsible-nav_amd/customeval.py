@@ -31,6 +31,10 @@ def main(argv=None):
     ap.add_argument("--resp-full", action="store_true",
                     help="also print the N x N responsibility matrix (every world agent as actor, the scripted "
                          "ones included) summed over the evaluation; runs the env with FeAR on")
+    ap.add_argument("--shield", type=float, default=None, metavar="TAU",
+                    help="responsibility shield: before every step, replace an RL action whose previewed FeAR "
+                         "exceeds TAU by an allowed one (the most probable under the actor); also prints how many "
+                         "agent-steps were replaced / had no allowed action")
     args = ap.parse_args(argv)
 
     from marlnav import scenario as S
@@ -50,11 +54,14 @@ def main(argv=None):
         m.load(args.checkpoint)
         actors = m.actors
     r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps, fear=args.feal or args.resp_full,
-                 seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full)
+                 seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
     print(f"Total steps: {r['steps']} across {n} episodes")
+    if args.shield is not None:
+        print(f"Shield (tau = {args.shield:g}): replaced {r['shield_replaced'].tolist()}, "
+              f"no allowed action {r['shield_stuck'].tolist()} agent-steps per RL agent")
     if args.feal:
         print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
     if args.resp_full:

@@ -26,14 +26,15 @@ LIB_PATH = os.path.join(CSRC, "libgridenv_measure.so" if MEASURE else "libgriden
 HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_ops.hip"),
                os.path.join(CSRC, "actor_ops.hip"), os.path.join(CSRC, "rollout_ops.hip"),
                os.path.join(CSRC, "maddpg_ops.hip"), os.path.join(CSRC, "patch_ops.hip"),
-               os.path.join(CSRC, "fear_full.hip")]
+               os.path.join(CSRC, "fear_full.hip"), os.path.join(CSRC, "fear_preview.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
                                    os.path.join(CSRC, "philox.h"), os.path.join(CSRC, "measure.h"),
                                    os.path.join(CSRC, "fear_alt_tasks.h"), os.path.join(CSRC, "dispatch.h"),
                                    os.path.join(CSRC, "obs_value.h"), os.path.join(CSRC, "obs_dest.h"),
-                                   os.path.join(CSRC, "resp_tables.h"), os.path.join(CSRC, "cf_env.h")]
+                                   os.path.join(CSRC, "resp_tables.h"), os.path.join(CSRC, "cf_env.h"),
+                                   os.path.join(CSRC, "draw_action.h"), os.path.join(CSRC, "fear_shield.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -194,7 +195,7 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
            "gw_set_fear_alt", "gw_fear_regret_accum",
            "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts",
-           "gw_set_feal", "gw_feal_accum", "gw_set_fear_full"]
+           "gw_set_feal", "gw_feal_accum", "gw_set_fear_full", "gw_fear_preview", "gw_fear_shield"]
 
 
 class GwObsSource(C.Structure):
@@ -352,6 +353,10 @@ def _declare(L):
     L.gw_feal_accum.restype = C.c_int
     L.gw_set_fear_full.argtypes = [p, p, p]
     L.gw_set_fear_full.restype = C.c_int
+    L.gw_fear_preview.argtypes = [p] * 7
+    L.gw_fear_preview.restype = C.c_int
+    L.gw_fear_shield.argtypes = [p, p, p, p, C.c_int64, C.c_int32, C.c_double, C.c_uint32, p, p, p]
+    L.gw_fear_shield.restype = C.c_int
     L.gw_affine_relu_fwd.argtypes = [p, p, p, p, C.c_int32, C.c_int64, C.c_int32, p]
     L.gw_affine_relu_fwd.restype = C.c_int
     L.gw_affine_relu_bwd.argtypes = [p] * 7 + [C.c_int32, C.c_int64, C.c_int32, p]
@@ -445,6 +450,43 @@ def check(status: int, what: str):
     if status != 0:
         msg = load().gw_last_error().decode(errors="replace")
         raise GwError(f"{what} failed (status {status}): {msg}")
+
+
+class graph_capture:
+    """``torch.cuda.graph(graph, **kw)`` with Python's cyclic garbage collector kept out of the capture.
+
+    A collection that falls inside a capture finalises whatever dead cycles exist at that moment, and those
+    own device objects: a dropped Rollout and its RolloutGraphs reference each other and hold HIP graphs,
+    streams, events and tensors.  Destroying those is no captured operation and must not happen while a stream
+    captures (a process was seen to abort in a collection inside Rollout.capture).  When the collector runs
+    depends only on how many Python objects were allocated, so any unrelated change moves it.  torch's own
+    context collects before a capture only with torch.compiler.config.force_cudagraph_gc, off by default, so:
+    collect now, outside the capture, and keep the collector off until the capture ends."""
+
+    def __init__(self, graph, **kw):
+        import torch
+        self._ctx = torch.cuda.graph(graph, **kw)
+        self._gc_was_on = False
+
+    def __enter__(self):
+        import gc
+        gc.collect()
+        self._gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            return self._ctx.__enter__()
+        except BaseException:
+            if self._gc_was_on:
+                gc.enable()
+            raise
+
+    def __exit__(self, *exc):
+        import gc
+        try:
+            return self._ctx.__exit__(*exc)
+        finally:
+            if self._gc_was_on:
+                gc.enable()
 
 
 class RecordingError(RuntimeError):

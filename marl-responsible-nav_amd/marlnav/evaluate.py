@@ -30,7 +30,7 @@ from .vec_env import VecGridEnv
 def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, max_steps: int = 150,
              fear: bool = False, seed: int = 42, record_actions: bool = False, fused: bool | None = None,
              variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False,
-             feal: bool = False, resp_full: bool = False) -> dict:
+             feal: bool = False, resp_full: bool = False, shield: float | None = None) -> dict:
     """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
     matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
     restricted agent j) summed over the episodes still running and divided by "steps".
@@ -43,7 +43,13 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
     resp_full (with ``fear=True``): the result also carries "resp_full", the [N, N] sum of every step's
     responsibility matrix with every world agent as actor (StepResult.resp_full: how much agent i, RL or
     scripted, restricted agent j) over the episodes still running (f64 CPU tensor; divide by "steps" for
-    the mean per env-step), and "resp_full_steps", the batched steps it covers."""
+    the mean per env-step), and "resp_full_steps", the batched steps it covers.
+    shield (a float tau; None: off): the responsibility shield at inference time.  Every step runs actor,
+    ``env.fear_preview`` of the proposed actions, ``env.fear_shield`` (the env's action mask, the actor's
+    probabilities, every RL agent shielded), then ``env.step`` with the shielded actions; works with
+    ``fear=False`` (the reference's evaluation configuration).  The result also carries "shield_replaced" [K]
+    and "shield_stuck" [K] (int64 CPU tensors): the agent-steps of the episodes still running whose action
+    was replaced / that had no allowed action.  Recorded actions are the ones applied."""
     if fear_regret and not fear:
         raise ValueError("evaluate(fear_regret=True) needs fear=True")
     if feal and not fear:
@@ -72,13 +78,22 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         feal_cnt = torch.zeros(2, dtype=torch.int64, device=dev)  # calls, env-steps
         full = torch.zeros((env.N, env.N), dtype=torch.float64, device=dev) if resp_full else None
         full_calls = torch.zeros((), dtype=torch.int64, device=dev)
+        table = torch.empty((episodes, env.K, 9), dtype=torch.float64, device=dev) if shield is not None else None
+        shield_cnt = torch.zeros((2, env.K), dtype=torch.int64, device=dev)  # replaced, stuck
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):
             if fused:  # one kernel over the obs descriptors (include/actor_ops.h)
-                actions, _ = actors.act_env(env, env.out["mask"], training=False)
+                actions, probs = actors.act_env(env, env.out["mask"], training=False)
             else:
-                actions, _ = actors.act(env.out["obs"], env.out["mask"], training=False)
+                actions, probs = actors.act(env.out["obs"], env.out["mask"], training=False)
+            if shield is not None:  # actor -> preview -> shield -> step; the episodes still running are counted
+                env.fear_preview(actions, out=table)
+                actions, flags = env.fear_shield(table, actions, mask=env.out["mask"], probs=probs.contiguous(),
+                                                 tau=float(shield))
+                on = active.to(torch.int64).unsqueeze(1)
+                shield_cnt[0] += ((flags & 1) * on).sum(0)
+                shield_cnt[1] += ((flags >> 1) * on).sum(0)
             if record_actions:
                 recorded.append(actions.clone())
             r = env.step(actions)
@@ -121,6 +136,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             out["feal"] = (feal_sum / max(c[2], 1)).cpu()
         if resp_full:
             out["resp_full"], out["resp_full_steps"] = full.cpu(), int(full_calls)
+        if shield is not None:
+            out["shield_replaced"], out["shield_stuck"] = shield_cnt[0].cpu(), shield_cnt[1].cpu()
         if record_actions:
             # the early-stop check runs every 8 steps: keep the actions up to the first step after
             # which every episode had ended (the steps an env-at-a-time loop would have taken)

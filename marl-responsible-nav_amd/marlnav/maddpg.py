@@ -712,7 +712,7 @@ class MADDPG:
                 self._graph = self._launches = rec
                 return rec
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _lib.graph_capture(g):
                 self._graph_out = self.learn(*draw())
                 if actor_env is not None:
                     # the graph writes this workspace on every replay: hold it as long as the graph
@@ -721,12 +721,12 @@ class MADDPG:
             self._graph = g
             return g
         g1, g2, g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1):
+        with _lib.graph_capture(g1):
             st, ac, rw, ns, dn, un, uc, ci = draw()
             ctx = self._learn_critic(st, ac, rw, ns, dn, un, ci)
-        with torch.cuda.graph(g2, pool=g1.pool()):
+        with _lib.graph_capture(g2, pool=g1.pool()):
             self._learn_actor(ctx, uc)
-        with torch.cuda.graph(g3, pool=g1.pool()):
+        with _lib.graph_capture(g3, pool=g1.pool()):
             self._graph_out = self._learn_finish(ctx)
         self._graph_ctx = ctx  # keeps the segments' shared tensors alive
         self._graphs = (g1, g2, g3)
@@ -763,7 +763,7 @@ class MADDPG:
         s.wait_stream(torch.cuda.current_stream(self.device))
         g = torch.cuda.CUDAGraph()
         with torch.cuda.stream(s):
-            with torch.cuda.graph(g):
+            with _lib.graph_capture(g):
                 self._graph_out = self.learn_desc(replay, actor_env=actor_env)
                 if fused_prep:
                     self._prep_ws, self._prep_env = self.actors._fast["ws"], actor_env

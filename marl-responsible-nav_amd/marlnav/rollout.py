@@ -180,7 +180,8 @@ class Rollout:
                  training: bool = True, group=None, seed: int = 0, fused: bool | None = None,
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
                  patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False,
-                 fear_regret: bool = False, feal: bool = False, resp_full: bool = False):
+                 fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
+                 shield: float | None = None):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -218,7 +219,13 @@ class Rollout:
         resp_full (an env built with ``fear_full=True``): every step's N x N responsibility matrix
         (StepResult.resp_full, every world agent as actor) is summed over the envs into a running [N, N]
         total (gw_fear_row_accum with K = N, one launch per step, also inside ``capture`` graphs);
-        ``totals()`` then carries "resp_full" and "resp_full_steps"."""
+        ``totals()`` then carries "resp_full" and "resp_full_steps".
+        shield (a float tau; None: off, no extra launch): the responsibility shield.  Every step runs actor,
+        then ``env.fear_preview`` of the proposed actions, then ``env.fear_shield`` (the env's action mask, the
+        actor's probabilities, every RL agent shielded), then ``env.step`` with the shielded actions.  The ring
+        keeps the actor's probabilities unchanged (the reference stores ``cont_actions``).  ``shield_flags``
+        holds the last step's [E, K] flags and ``totals()`` carries "shield_replaced" [K] and "shield_stuck"
+        [K].  Eager only: ``capture`` raises ValueError.  Works with FeAR off (``fear=False``) too."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -301,6 +308,29 @@ class Rollout:
                 raise ValueError("Rollout(resp_full=True) needs VecGridEnv(fear_full=True)")
             self._full = torch.zeros((env.N, env.N), dtype=torch.float64, device=env.device)
             self._full_steps = torch.zeros((), dtype=torch.int64, device=env.device)
+        self.shield = None if shield is None else float(shield)
+        self.shield_flags = None  # the last step's [E, K] uint8 flags (VecGridEnv.fear_shield)
+        self._shield_cnt = None
+        if self.shield is not None:
+            self._shield_cnt = torch.zeros((2, env.K), dtype=torch.int64, device=env.device)  # replaced, stuck
+            self._shield_table = torch.empty((env.E, env.K, 9), dtype=torch.float64, device=env.device)
+            self._shield_joint = torch.empty((env.E, env.N), dtype=torch.int32, device=env.device)
+            self._shield_out = torch.empty((env.E, env.K), dtype=torch.int32, device=env.device)
+            self.shield_flags = torch.zeros((env.E, env.K), dtype=torch.uint8, device=env.device)
+
+    def _shielded(self, actions, probs, mask):
+        """actor -> preview -> shield: the actions the step will apply, and the flags into the totals."""
+        env = self.env
+        if actions is None:  # the device-random policy: the preview reports the actions the step would draw
+            env.fear_preview(None, out=self._shield_table, actions=self._shield_joint)
+            actions = self._shield_joint[:, :env.K].contiguous()
+        else:
+            env.fear_preview(actions, out=self._shield_table)
+        out, flags = env.fear_shield(self._shield_table, actions, mask=mask, probs=probs, tau=self.shield,
+                                     out=self._shield_out, flags=self.shield_flags)
+        self._shield_cnt[0] += (flags & 1).sum(0)
+        self._shield_cnt[1] += (flags >> 1).sum(0)
+        return out
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0
@@ -464,6 +494,8 @@ class Rollout:
             actions, probs = self.actors.act(self._obs_now(), mask, self.training, generator=self.gen)
         else:
             actions, probs = None, None  # device-RNG random policy
+        if self.shield is not None:  # beside the previous step's FeAR kernels (the preview has its own record buffer)
+            actions = self._shielded(actions, probs, mask)
         self._flush()  # after the actor: it overlapped the previous step's FeAR kernel
         if self.replay is not None:
             rp = self.replay
@@ -556,6 +588,8 @@ class Rollout:
         after at least one step; a ReturnGather (if any) with window == n and nothing pending.
         Nothing runs at capture: the state is untouched until the first replay."""
         env, rp = self.env, self.replay
+        if self.shield is not None:
+            raise ValueError("Rollout.capture: the responsibility shield (shield=tau) is eager-only")
         if not (self.fused and rp is not None and not self.distributed and self._dev_counter()):
             raise _lib.GwError("Rollout.capture: the fused actor, a replay ring and one rank")
         if rp.S % n:
@@ -580,7 +614,7 @@ class Rollout:
                 torch.cuda.synchronize(env.device)
                 for _ in range(rp.S // n):
                     cg = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(cg):
+                    with _lib.graph_capture(cg):
                         env.profile(False)
                         for _i in range(n):
                             # the CNN listing (gw_patch_cnn_write_list) never crosses a graph
@@ -617,11 +651,24 @@ class Rollout:
         With ``resp_full``: "resp_full", the [N, N] sum of every step's and env's responsibility matrix
         (f64 CPU tensor, all-reduced with the rest), and "resp_full_steps", this rank's steps (like
         "resp_steps": the ranks step in lockstep, so the count is not summed over them).
+        With ``shield``: "shield_replaced" [K] and "shield_stuck" [K] (int64 CPU tensors): the agent-steps whose
+        action the shield replaced (flag bit 0) / that had no allowed action (flag bit 1).
         With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
         the responsibility total): every rank calls it."""
         if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
-                and self._full is None):
+                and self._full is None and self._shield_cnt is None):
             return {}
+        if self._shield_cnt is not None:  # its own small all-reduce: exact integer counts
+            cnt = self._shield_cnt.clone()
+            if self.distributed:
+                dist.all_reduce(cnt, group=self.group)
+            shield = {"shield_replaced": cnt[0].cpu(), "shield_stuck": cnt[1].cpu()}
+            if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
+                    and self._full is None):
+                self._flush()
+                return shield
+        else:
+            shield = {}
         self._flush()
         nst = _lib.GW_STATS if self._acc is not None else 0
         parts = [self._acc.sum(0)] if nst else []
@@ -657,6 +704,7 @@ class Rollout:
             N = self.env.N
             out["resp_full"] = local[nst:nst + N * N].reshape(N, N).cpu()
             out["resp_full_steps"] = int(self._full_steps)
+        out.update(shield)
         return out
 
     def completed_scores(self, last: int | None = None):

@@ -414,7 +414,7 @@ class VecGridEnv:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)
-            with torch.cuda.graph(g):
+            with _lib.graph_capture(g):
                 self.profile(False)
                 for i in range(n):
                     self.step(into=gather.into() if gather is not None else None)
@@ -525,6 +525,59 @@ class VecGridEnv:
         _lib.check(self.lib.gw_set_fear_full(self.handle, _ptr(resp_full), _ptr(resp_valid)), "gw_set_fear_full")
         self.out["resp_full"], self.out["resp_valid"] = resp_full, resp_valid
         self._into_cache.clear()  # the cached StepResults carry the old views
+
+    def fear_preview(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None, actions: torch.Tensor | None = None,
+                     mdr: torch.Tensor | None = None) -> torch.Tensor:
+        """The per-action FeAR table of the step that ``step(rl_actions, scripted)`` would run next, without
+        moving the world (gw_fear_preview): -> [E, K, 9] float64, what ``StepResult.fear_alt`` of that step
+        would hold, bit for bit.  None arguments mean what they mean for ``step`` (the device-random RL policy /
+        the scenario policy, with the step's own Philox counters).  Works with ``fear=False`` too.
+        out: the [E, K, 9] float64 destination (default: a new tensor); actions / mdr: optional [E, N] int32
+        outputs, the joint action that step will apply and the current cells' MdR.  Changes no env state."""
+        E, K, N = self.E, self.K, self.N
+        rl = self._as_i32(rl_actions, (E, K))
+        sa = self._as_i32(scripted, (E, N - K))
+        if out is None:
+            out = torch.empty((E, K, 9), dtype=torch.float64, device=self.device)
+        for t, dt, n, name in ((out, torch.float64, E * K * 9, "out"), (actions, torch.int32, E * N, "actions"),
+                               (mdr, torch.int32, E * N, "mdr")):
+            if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"fear_preview({name}=...): need a contiguous {dt} tensor of {n} elements on "
+                                 f"{self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_fear_preview(self.handle, _ptr(rl), _ptr(sa), _ptr(out), _ptr(actions), _ptr(mdr),
+                                                self._stream()), "gw_fear_preview")
+        return out
+
+    def fear_shield(self, table: torch.Tensor, actions: torch.Tensor, mask: torch.Tensor | None = None,
+                    probs: torch.Tensor | None = None, tau: float = 0.0, agents: int | None = None,
+                    out: torch.Tensor | None = None, flags: torch.Tensor | None = None):
+        """The responsibility shield (gw_fear_shield): -> (actions [E, K] int32, flags [E, K] uint8).  An RL
+        action whose previewed FeAR ``table[e, k, a]`` (``fear_preview`` of the proposed ``actions``) exceeds
+        ``tau`` is replaced by an allowed one (mask bit set, FeAR <= tau): the most probable under ``probs``
+        [K, E, 9] float32, or without probs the least FeAR; ties to the lowest action.  flags: 0 kept, 1
+        replaced, 2 no allowed action and the least-FeAR masked one was the proposed one, 3 that one replaced
+        it.  mask: [E, K] int16 9-bit action masks (None: all nine); agents: bitmask of the shielded RL agents
+        (None: all K).  out may be ``actions`` itself.  The shield is unilateral: each row assumes the other
+        agents keep their proposed actions (include/rollout_ops.h)."""
+        E, K = self.E, self.K
+        act = self._as_i32(actions, (E, K))
+        if out is None:
+            out = torch.empty((E, K), dtype=torch.int32, device=self.device)
+        if flags is None:
+            flags = torch.empty((E, K), dtype=torch.uint8, device=self.device)
+        for t, dt, n, name in ((table, torch.float64, E * K * 9, "table"), (mask, torch.int16, E * K, "mask"),
+                               (probs, torch.float32, K * E * 9, "probs"), (out, torch.int32, E * K, "out"),
+                               (flags, torch.uint8, E * K, "flags")):
+            if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"fear_shield({name}=...): need a contiguous {dt} tensor of {n} elements on "
+                                 f"{self.device}")
+        bits = (1 << K) - 1 if agents is None else int(agents) & 0xFFFFFFFF
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_fear_shield(_ptr(table), _ptr(act), _ptr(mask), _ptr(probs), E, K, float(tau), bits,
+                                               _ptr(out), _ptr(flags), self._stream()), "gw_fear_shield")
+        return out, flags
 
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
