@@ -388,9 +388,12 @@ gw_status gw_obs_dest_forget(void *env, const void *ptr);
 gw_status gw_obs_delta_counts(void *env, int64_t out[2]);
 
 /* The FeAR kernel's envs per block, before the first gw_reset (it fixes gw_stats_rows: size the
- * stats buffer after it): wide = 1 (the default: half the resident waves, best beside the full-obs
- * writer), 0 = narrow (twice the waves, best where FeAR is on the critical path: an env that writes
- * no full obs, e.g. the local-window rollouts; c5patch 115 -> 111-112 us per step).
+ * stats buffer after it): wide = 1, 0 = narrow (half the envs per block).  The rule for the default:
+ * wide for f32 obs (gw_create), narrow once gw_set_obs_dtype selects bf16 obs before the first
+ * gw_reset; a caller whose env writes no full obs (the local-window rollouts) asks for narrow here
+ * (c5patch 115 -> 111-112 us per step).  fear_v2's wide blocks are 64 envs on 256 threads (one lane
+ * per (env, actor) in its per-env phases, four waves for the counterfactual sims), its narrow blocks
+ * and fear_rows_kernel's blocks 128 threads; the statistics rows depend on the envs per block only.
  * GW_FEAR_BE=wide|narrow in the environment overrides it.  GW_ERR_STATE after gw_reset. */
 gw_status gw_set_fear_blocks(void *env, int wide);
 gw_status gw_obs_fence(void *env, void *stream);

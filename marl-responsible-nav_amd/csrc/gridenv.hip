@@ -873,19 +873,29 @@ __global__ void __launch_bounds__(DELTA_T) obs_delta_kernel(Params p, float *__r
 #ifndef GW_NOFEAR_BE  // envs per block of the FeAR-off step_v2 with N <= 4 (measurement builds: 16)
 #define GW_NOFEAR_BE 32
 #endif
+#ifndef GW_DEF_BE  // envs per block of the deferred-FeAR world update with K <= 2, N <= 4 (measurement builds: 32)
+#define GW_DEF_BE 128
+#endif
+#ifndef GW_FEAR_T  // threads per wide fear_v2 block (measurement builds: 128)
+#define GW_FEAR_T 256
+#endif
 // DEF: the deferred-FeAR world-update kernel (step_v2<.., DEFER>, GW_KERNEL=defer with FeAR on):
-// one env per thread in 128-env blocks (it runs beside the large obs writer, where per-block
-// table fills and barriers cost more than the lane-parallel draws save)
-template <int N, int KMAX, bool FEAR, bool WIDE = false, bool DEF = false> struct V2Cfg {
-    static constexpr int THREADS = 128;
+// one env per thread in 128-env blocks.  32-env blocks with the FeAR-off kernel's lane-parallel
+// draws (-DGW_DEF_BE=32) were measured at C3 without the full obs writer beside them and are
+// 1.0 us per step slower (profiles/chain_shapes): per-block table fills and barriers still cost
+// more than the parallel draws save.
+// TT: threads per block (fear_v2's wide blocks: GW_FEAR_T; every other kernel 128)
+template <int N, int KMAX, bool FEAR, bool WIDE = false, bool DEF = false, int TT = 128> struct V2Cfg {
+    static constexpr int THREADS = TT;
     // WIDE (fear_v2, GW_FEAR_BE=wide): twice the envs per block, half the resident waves
     static constexpr int BE = (WIDE ? 2 : 1) *
         (FEAR ? (KMAX <= 2 ? (N <= 4 ? 32 : 16) : (N <= 4 ? 16 : 4))
-              : (KMAX <= 2 && (N > 4 || DEF) ? 128 : GW_NOFEAR_BE));
+              : (KMAX <= 2 && N > 4 ? 128 : (DEF && KMAX <= 2 ? GW_DEF_BE : GW_NOFEAR_BE)));
     // FeAR off with 32 envs per block: the 128 threads draw the (env, agent) actions in parallel
     // before one thread per env runs the rest (step_v2_block); with 128 envs per block (N > 4,
     // large batches) each env thread draws its own
     static constexpr bool XDRAW = !FEAR && BE <= 32 && N <= 4;
+    static_assert(!FEAR || BE * KMAX <= THREADS, "fear_block: one lane per (env, actor)");
     static_assert(!FEAR || BE <= 64, "task encoding holds 6 env bits");
     // task list: [env sims (step_v2 only: BE)][base sims: 2 per actor k with act != MdR] then
     // groups of 16 counterfactuals (one entry per (actor k, close j), expanded on the fly)
@@ -899,9 +909,9 @@ template <int N, int KMAX, bool FEAR, bool WIDE = false, bool DEF = false> struc
     }
 };
 
-template <int N, int KMAX, bool FEAR, bool WIDE = false, bool DEF = false>
+template <int N, int KMAX, bool FEAR, bool WIDE = false, bool DEF = false, int TT = 128>
 struct alignas(16) V2Shared {
-    using Cfg = V2Cfg<N, KMAX, FEAR, WIDE, DEF>;
+    using Cfg = V2Cfg<N, KMAX, FEAR, WIDE, DEF, TT>;
     static constexpr int BE = Cfg::BE, FB = FEAR ? BE : 1;
     double red[Cfg::THREADS / 64][GW_STATS];
     typename Cfg::Task tasks[Cfg::MAXB];
@@ -913,8 +923,9 @@ struct alignas(16) V2Shared {
     int8_t act[FB][N];
     int8_t mdr[FB][N];
     uint8_t close[FB][KMAX];
-    uint8_t base[FB][KMAX][2];
-    uint8_t cj[FB][KMAX][FEAR ? N : 1][2][NA];
+    // FeAR: the 9-bit valid sets of (env, actor k, affected agent j): bit b = j ends valid when it
+    // plays b, bits 0-8 with k on its MdR, bits 16-24 with k on its own action (fear_record)
+    uint32_t vset[FB][KMAX][FEAR ? N : 1];
     uint2 wl[(N >= GW_LIST_MIN_N) ? Cfg::THREADS * N : 1];  // World<N, true> rows (one per thread)
     int8_t xact[Cfg::XDRAW ? BE : 1][N];   // FeAR off: the (env, agent) threads' action draws and MdRs
     int8_t xmdr[Cfg::XDRAW ? BE : 1][N];
@@ -930,41 +941,36 @@ __device__ __forceinline__ void select_actions_v2(const Params &p, int64_t e, co
     for (int n = 0; n < N; ++n) act[n] = draw_action(p, e, n, es.episode, es.t, es.pos[n], ctab, cdf_s);
 }
 
-// FeAR phase A of one env (custom/ma_customenv.py:247-251, Responsibility.py:135-210): close sets
-// (:456-464) into sh.close and the de-duplicated counterfactual task list appended to sh.tasks.
-// Expects sh.pos / sh.act / sh.mdr of the env filled.
+// FeAR phase A of one (env, actor k) (custom/ma_customenv.py:247-251, Responsibility.py:135-210):
+// k's close set (:456-464) into sh.close, its valid sets zeroed, and, unless k plays its MdR, its
+// de-duplicated counterfactual tasks appended to sh.tasks / sh.groups.  Expects sh.pos / sh.act /
+// sh.mdr of the env filled by the time phase B starts (it reads pos / act / mdr_k from registers).
 template <int N, int KMAX, class Sh>
-__device__ __forceinline__ void fear_plan(const Params &p, Sh &sh, int el, const int (&pos)[N], const int (&act)[N],
-                                          int off0) {
+__device__ __forceinline__ void fear_plan_actor(const Params &p, Sh &sh, int el, int k, const int (&pos)[N],
+                                                const int (&act)[N], int mdr_k, int off0) {
     using Cfg = typename Sh::Cfg;
-    const int K = p.K;
-    int nb = 0, ng = 0;
-    uint32_t close[KMAX];
+    int pk = pos[0], ak = act[0];
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        close[k] = 0;
-        if (k >= K) continue;
-#pragma unroll
-        for (int n = 0; n < N; ++n)
-            if (n == k || manhattan(p, pos[k], pos[n]) <= 5) close[k] |= 1u << n;
-        sh.close[el][k] = (uint8_t)close[k];
-        if (act[k] != (int)sh.mdr[el][k]) {
-            nb += 2;
-            ng += __popc(close[k]) - 1;
-        }
+    for (int n = 1; n < N; ++n) {
+        pk = (n == k) ? pos[n] : pk;
+        ak = (n == k) ? act[n] : ak;
     }
-    if (!nb) return;
-    int sb = off0 + atomicAdd(&sh.nbase, nb);
+    uint32_t close = 0;
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+        if (n == k || manhattan(p, pk, pos[n]) <= 5) close |= 1u << n;
+    sh.close[el][k] = (uint8_t)close;
+#pragma unroll
+    for (int n = 0; n < N; ++n) sh.vset[el][k][n] = 0u;
+    if (ak == mdr_k) return;
+    const int ng = __popc(close) - 1;
+    int sb = off0 + atomicAdd(&sh.nbase, 2);
     int sg = ng ? atomicAdd(&sh.ngroup, ng) : 0;
+    sh.tasks[sb] = Cfg::enc(el, k, 0, 0, 15);
+    sh.tasks[sb + 1] = Cfg::enc(el, k, 0, 1, 15);
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (k >= K || act[k] == (int)sh.mdr[el][k]) continue;
-        sh.tasks[sb++] = Cfg::enc(el, k, 0, 0, 15);
-        sh.tasks[sb++] = Cfg::enc(el, k, 0, 1, 15);
-#pragma unroll
-        for (int j = 0; j < N; ++j)
-            if (j != k && ((close[k] >> j) & 1u)) sh.groups[sg++] = Cfg::enc(el, k, j, 0, 0);
-    }
+    for (int j = 0; j < N; ++j)
+        if (j != k && ((close >> j) & 1u)) sh.groups[sg++] = Cfg::enc(el, k, j, 0, 0);
 }
 
 // Task ti of phase B: entries [0, nb_end) are stored; past them, group g = (ti - nb_end) / 16
@@ -978,6 +984,26 @@ __device__ __forceinline__ uint32_t fear_task_at(const Sh &sh, int ti, int nb_en
     const int bi = s & 7;
     const int b = bi + (bi >= (int)sh.act[el][j]);
     return tk | ((uint32_t)b << 6) | ((uint32_t)(s >> 3) << 10);
+}
+
+// One counterfactual's outcome into the valid sets of (env, actor k), half var (0: k on its MdR,
+// 1: on its own action): an alternative b of agent j ORs bit b of j's set; the base sim (b == 15)
+// supplies bit act[n] of every close agent n and all nine bits of an agent outside the close set,
+// which stays whatever the others play (9 x valid(base)).  LDS atomics without a return value.
+template <int N, class Sh>
+__device__ __forceinline__ void fear_record(Sh &sh, int el, int k, int j, int var, int b, uint32_t valid) {
+    const int sft = 16 * var;
+    if (b != 15) {
+        if ((valid >> j) & 1u) atomicOr(&sh.vset[el][k][j], 1u << (sft + b));
+        return;
+    }
+    const uint32_t cl = sh.close[el][k];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        if (n == k || !((valid >> n) & 1u)) continue;
+        const uint32_t bits = ((cl >> n) & 1u) ? 1u << (int)sh.act[el][n] : 0x1FFu;
+        atomicOr(&sh.vset[el][k][n], bits << sft);
+    }
 }
 
 // FeAR phase B, one counterfactual world update (task bits: see V2Cfg::enc): the joint action
@@ -1005,59 +1031,38 @@ __device__ __forceinline__ void fear_task(const Params &p, Sh &sh, uint32_t tk, 
     if constexpr (LIST) w.lw = &sh.wl[threadIdx.x * N];
     uint32_t caught;
     simulate<N, true>(w, okv, 0, apple, caught, fin);
-    const uint32_t valid = ~(w.crash | w.restr) & ((1u << N) - 1u);
-    if (b == 15)
-        sh.base[el][k][var] = (uint8_t)valid;
-    else
-        sh.cj[el][k][j][var][b] = (uint8_t)((valid >> j) & 1u);
+    fear_record<N>(sh, el, k, j, var, b, ~(w.crash | w.restr) & ((1u << N) - 1u));
 }
 
-// FeAR phase C of one env: V counts -> Resp table -> np.sum of the Resp row in numpy's order.
-// The Resp row itself goes to gw_step_out.fear_row[e][k][.] when that output is set (uniform per
-// launch): an explicit zero row for an actor the de-duplication skipped (act == MdR: the
-// reference's vm == va there, Resp = 0.0).
+// FeAR phase C of one (env, actor k): popcounts of the valid sets = the V counts -> Resp row ->
+// np.sum of the row in numpy's order.  The row itself goes to gw_step_out.fear_row[e][k][.] when
+// that output is set (uniform per launch): an explicit zero row for an actor the de-duplication
+// skipped (act == MdR: the reference's vm == va there, Resp = 0.0).
 template <int N, int KMAX, class Sh>
-__device__ __forceinline__ void fear_values(const Params &p, const Sh &sh, int el, int64_t e, const int (&act)[N],
-                                            const int (&mdr)[N], const double *resp_s, double (&fear)[MAXN]) {
+__device__ __forceinline__ double fear_value(const Params &p, const Sh &sh, int el, int64_t e, int k, bool skipped,
+                                             const double *resp_s) {
+    double *row = p.out.fear_row ? p.out.fear_row + (e * p.K + k) * N : nullptr;
+    if (skipped) {
+        if (row)
 #pragma unroll
-    for (int k = 0; k < MAXN; ++k) fear[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (k >= p.K) continue;
-        double *row = p.out.fear_row ? p.out.fear_row + (e * p.K + k) * N : nullptr;
-        if (act[k] == mdr[k]) {
-            if (row)
-#pragma unroll
-                for (int jj = 0; jj < N; ++jj) row[jj] = 0.0;
-            continue;
-        }
-        const uint32_t cl = sh.close[el][k];
-        const uint32_t b0 = sh.base[el][k][0], b1 = sh.base[el][k][1];
-        double resp[N];
-#pragma unroll
-        for (int jj = 0; jj < N; ++jj) {
-            resp[jj] = 0.0;
-            if (jj == k) {
-                if (row) row[jj] = 0.0;
-                continue;
-            }
-            int vm, va;
-            if ((cl >> jj) & 1u) {
-                vm = 0;
-                va = 0;
-                for (int b = 0; b < NA; ++b) {
-                    vm += (b == act[jj]) ? (int)((b0 >> jj) & 1u) : (int)sh.cj[el][k][jj][0][b];
-                    va += (b == act[jj]) ? (int)((b1 >> jj) & 1u) : (int)sh.cj[el][k][jj][1][b];
-                }
-            } else {
-                vm = 9 * (int)((b0 >> jj) & 1u);
-                va = 9 * (int)((b1 >> jj) & 1u);
-            }
-            resp[jj] = resp_s[vm * 10 + va];
-            if (row) row[jj] = resp[jj];
-        }
-        fear[k] = np_sum_row<N>(resp, k);
+            for (int jj = 0; jj < N; ++jj) row[jj] = 0.0;
+        return 0.0;
     }
+    double resp[N];
+#pragma unroll
+    for (int jj = 0; jj < N; ++jj) {
+        resp[jj] = 0.0;
+        if (jj != k) {
+            const uint32_t v = sh.vset[el][k][jj];
+            resp[jj] = resp_s[__popc(v & 0x1FFu) * 10 + __popc(v >> 16)];
+        }
+        if (row) row[jj] = resp[jj];
+    }
+    double sum = 0.0;  // np_sum_row with the row as a constant (k is uniform per wave in fear_block's wide blocks)
+#pragma unroll
+    for (int kk = 0; kk < KMAX; ++kk)
+        if (kk == k) sum = np_sum_row<N>(resp, kk);
+    return sum;
 }
 
 // Block statistics: deterministic wave butterfly + fixed-order cross-wave sum, one row per block.
@@ -1081,6 +1086,7 @@ __device__ __forceinline__ void block_stats(const Params &p, Contrib &ct, double
 }
 
 #ifdef GW_STEP_CLK  // measurement build only (tools/step_clk.sh): thread 0's phase stamps per block
+// (slots 0-6 and 15: step_v2_block; 8-13: fear_block)
 __device__ unsigned long long g_step_clk[64][16];
 #define STEP_STAMP(slot)                                                             \
     do {                                                                             \
@@ -1165,7 +1171,9 @@ __device__ __forceinline__ void step_v2_block(const Params &p, int64_t bid, V2Sh
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) sh.apple[tid][k] = (k < K && ((es.flags >> k) & 1u)) ? p.apples[k] : -1;
             sh.tasks[tid] = Cfg::enc(tid, 0, 0, 0, 0);
-            fear_plan<N, KMAX>(p, sh, tid, es.pos, act, BE);
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k < K) fear_plan_actor<N, KMAX>(p, sh, tid, k, es.pos, act, (int)sh.mdr[tid][k], BE);
         }
         __syncthreads();
         // ---- B ----
@@ -1212,11 +1220,7 @@ __device__ __forceinline__ void step_v2_block(const Params &p, int64_t bid, V2Sh
                 for (int n = 0; n < N; ++n) sh.fin[el][n] = fin[n];
                 sh.bits[el] = w.crash | (w.restr << 8) | (caught << 16);
             } else {
-                const uint32_t valid = ~(w.crash | w.restr) & ((1u << N) - 1u);
-                if (b == 15)
-                    sh.base[el][k][var] = (uint8_t)valid;
-                else
-                    sh.cj[el][k][j][var][b] = (uint8_t)((valid >> j) & 1u);
+                fear_record<N>(sh, el, k, j, var, b, ~(w.crash | w.restr) & ((1u << N) - 1u));
             }
         }
         __syncthreads();
@@ -1231,7 +1235,11 @@ __device__ __forceinline__ void step_v2_block(const Params &p, int64_t bid, V2Sh
                 fin[n] = sh.fin[tid][n];
             }
             double fear[MAXN];
-            fear_values<N, KMAX>(p, sh, tid, e, act, mdr, resp_s, fear);
+#pragma unroll
+            for (int k = 0; k < MAXN; ++k) fear[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k < K) fear[k] = fear_value<N, KMAX>(p, sh, tid, e, k, act[k] == mdr[k], resp_s);
             const uint32_t bits = sh.bits[tid];
             ObsInfo<N> oi;
             // inline FeAR with the fear_alt table or FeAL armed (uniform per launch): the record their kernels read
@@ -1346,13 +1354,19 @@ __global__ void __launch_bounds__(128) step_obs(Params p, Params q, float *__res
 // updates overlap the HBM-store-bound obs_kernel.  Inputs: the FearRec of each env (pre-step
 // cells, joint action, env rewards, done) and score / fear_score; same phases A/B/C as step_v2
 // without the env's own update.  Dynamic LDS: [cell table][Resp 100 f64] (no CDFs).
+// Phases A and C run on one lane per (env, actor): lane i = env i % BE, actor i / BE, so actor 0's
+// lane is lane el, the env's place in the statistics butterfly, and runs the env's tail.  The wide
+// fear_v2 blocks are 64 envs on GW_FEAR_T = 256 threads (phase B's sims in half the rounds; the
+// lanes past the envs add 0.0 to the statistics, so the rows are those of 128 threads);
+// fear_rows_kernel and the narrow blocks have 128 threads (profiles/chain_shapes).
 // ---------------------------------------------------------------------------------------
-template <int N, int KMAX, bool WIDE>
+template <int N, int KMAX, bool WIDE, int T>
 __device__ __forceinline__ void fear_block(const Params &p, uint32_t bid) {
-    using Cfg = V2Cfg<N, KMAX, true, WIDE>;
-    using Sh = V2Shared<N, KMAX, true, WIDE>;
-    constexpr int BE = Cfg::BE, T = Cfg::THREADS;
+    using Cfg = V2Cfg<N, KMAX, true, WIDE, false, T>;
+    using Sh = V2Shared<N, KMAX, true, WIDE, false, T>;
+    constexpr int BE = Cfg::BE;
     __shared__ Sh sh;
+    __shared__ double xfear[KMAX][BE];  // phase C's FeAR of (actor, env) for the env's tail lane
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
     uint32_t *ctab = reinterpret_cast<uint32_t *>(dyn + p.ctab_off);
     double *resp_s = reinterpret_cast<double *>(dyn + p.resp_off);
@@ -1362,54 +1376,69 @@ __device__ __forceinline__ void fear_block(const Params &p, uint32_t bid) {
     const int64_t e0 = p.e_begin + (int64_t)bid * BE;
     const int nenv = (int)min((int64_t)BE, p.e_end - e0);
     const int K = p.K;
+    STEP_STAMP(8);
+    // phases A and C: one lane per (env, actor); the env's lane of actor 0 is lane el, which also
+    // runs the env's tail (the statistics butterfly sums the envs in that lane order)
+    const int el = tid % BE, ka = tid / BE;
+    const bool live = ka < KMAX && ka < K && el < nenv, tail = tid < nenv;
     int pos[N], act[N], rew[MAXN];
     uint32_t bonus = 0;
     bool done = false;
     double score0 = 0.0, fscore0 = 0.0;
-    if (tid < nenv) {
-        const int64_t e = e0 + tid;
-        load_fear_rec<N>(p, e, pos, act, rew, bonus, done);
-        score0 = p.st.score[e];
-        fscore0 = p.st.fscore[e];
+    if (live) load_fear_rec<N>(p, e0 + el, pos, act, rew, bonus, done);
+    if (tail) {
+        score0 = p.st.score[e0 + tid];
+        fscore0 = p.st.fscore[e0 + tid];
     }
     lds_fill<T>(ctab, p.tb.celltab, p.HW, tid);
     lds_fill<T>(reinterpret_cast<uint32_t *>(resp_s), reinterpret_cast<const uint32_t *>(p.tb.resp), 200, tid);
     if (tid == 0) sh.nbase = sh.ngroup = 0;
     __syncthreads();
+    STEP_STAMP(9);
     const CtabOk okv{ctab};
     // ---- A ----
-    int mdr[N];
-    if (tid < nenv) {
+    bool skipped = true;  // the actor plays its MdR: no tasks, Resp row 0
+    if (live) {
+        int mdr_k = 0;
 #pragma unroll
         for (int n = 0; n < N; ++n) {
-            mdr[n] = (int)((ctab[pos[n]] >> CT_MDR) & 0xFu);
-            sh.pos[tid][n] = pos[n];
-            sh.act[tid][n] = (int8_t)act[n];
-            sh.mdr[tid][n] = (int8_t)mdr[n];
+            const int m = (int)((ctab[pos[n]] >> CT_MDR) & 0xFu);
+            if (n == ka) {
+                mdr_k = m;
+                skipped = act[n] == m;
+            }
+            if (tail) {
+                sh.pos[el][n] = pos[n];
+                sh.act[el][n] = (int8_t)act[n];
+                sh.mdr[el][n] = (int8_t)m;
+            }
         }
-        fear_plan<N, KMAX>(p, sh, tid, pos, act, 0);
+        fear_plan_actor<N, KMAX>(p, sh, el, ka, pos, act, mdr_k, 0);
     }
     __syncthreads();
+    STEP_STAMP(10);
     // ---- B ----
     const int nb_end = sh.nbase, ntask = nb_end + 16 * sh.ngroup;
     if (tid == 0 && p.sims && ntask) atomicAdd(p.sims, (unsigned long long)ntask);
     for (int ti = tid; ti < ntask; ti += T) fear_task<N, KMAX>(p, sh, fear_task_at(sh, ti, nb_end), okv);
     __syncthreads();
+    STEP_STAMP(11);
     // ---- C ----
+    if (live) xfear[ka][el] = fear_value<N, KMAX>(p, sh, el, e0 + el, ka, skipped, resp_s);
+    __syncthreads();
     Contrib ct;
     contrib_zero(ct);
-    if (tid < nenv) {
+    if (tail) {
         const int64_t e = e0 + tid;
-        double fear[MAXN];
-        fear_values<N, KMAX>(p, sh, tid, e, act, mdr, resp_s, fear);
         double shaped[MAXN], fsum_in[MAXN];
 #pragma unroll
         for (int k = 0; k < MAXN; ++k) {
             shaped[k] = fsum_in[k] = 0.0;
-            if (k >= K) continue;
+            if (k >= K || k >= KMAX) continue;
+            const double fear = xfear[k][tid];
             const double r = ((bonus >> k) & 1u) ? __dadd_rn((double)rew[k], 0.1) : (double)rew[k];
-            shaped[k] = __dadd_rn(__dmul_rn(p.fear_weight, fear[k]), r);  // agent.py:130
-            fsum_in[k] = fear[k];
+            shaped[k] = __dadd_rn(__dmul_rn(p.fear_weight, fear), r);  // agent.py:130
+            fsum_in[k] = fear;
         }
         const double score = __dadd_rn(score0, np_sum_small(shaped, K));    // agent.py:173
         const double fscore = __dadd_rn(fscore0, np_sum_small(fsum_in, K));  // agent.py:141
@@ -1418,7 +1447,7 @@ __device__ __forceinline__ void fear_block(const Params &p, uint32_t bid) {
         for (int k = 0; k < KMAX; ++k) {
             if (k >= K) continue;
             const int64_t ek = e * K + k;
-            if (o.fear) o.fear[ek] = fear[k];
+            if (o.fear) o.fear[ek] = fsum_in[k];
             if (o.shaped) o.shaped[ek] = shaped[k];
         }
         if (o.ep_return) o.ep_return[e] = score;
@@ -1430,12 +1459,14 @@ __device__ __forceinline__ void fear_block(const Params &p, uint32_t bid) {
         ct.v[2] = np_sum_small(fsum_in, K);
         ct.v[5] = np_sum_small(shaped, K);
     }
+    STEP_STAMP(12);
     block_stats<T, ST_F64_FEAR, 0u>(p, ct, sh.red, tid, p.stats_row0 + e0 / BE);
+    STEP_STAMP(13);
 }
 
 template <int N, int KMAX, bool WIDE>
-__global__ void __launch_bounds__(128) fear_v2(Params p) {
-    fear_block<N, KMAX, WIDE>(p, blockIdx.x);
+__global__ void __launch_bounds__(WIDE ? GW_FEAR_T : 128) fear_v2(Params p) {
+    fear_block<N, KMAX, WIDE, WIDE ? GW_FEAR_T : 128>(p, blockIdx.x);
 }
 
 // fear_v2 and the step's P x P windows (gw_step_patch_next; the row writer of csrc/window_rows.h on
@@ -1444,7 +1475,7 @@ __global__ void __launch_bounds__(128) fear_v2(Params p) {
 template <int N, int KMAX, bool WIDE>
 __global__ void __launch_bounds__(128) fear_rows_kernel(Params p, PatchArgs a, uint32_t nfear, uint32_t nrx) {
     if (blockIdx.x < nfear) {
-        fear_block<N, KMAX, WIDE>(p, blockIdx.x);
+        fear_block<N, KMAX, WIDE, 128>(p, blockIdx.x);
         return;
     }
     // the rows' LDS slices in the dynamic region the FeAR blocks use for their tables.  One launch
@@ -1463,7 +1494,7 @@ __global__ void __launch_bounds__(128) fear_rows_kernel(Params p, PatchArgs a, u
 // csrc/fear_alt_tasks.h: per actor 9 variants x (1 base + 8 alternatives of each close agent).
 // A sim ORs the affected agent's valid bit into the 9-bit set vb[k][a][j] (bit b = j valid under
 // its action b; the base sim supplies bit act[j], and all nine bits of an agent outside the close
-// set, which stays: 9 * valid(base) as fear_values); popcounts give the V counts.  The MdR variant
+// set, which stays: 9 * valid(base) as fear_record); popcounts give the V counts.  The MdR variant
 // is one of the nine, so Resp[k][j](a) = tab[V(mdr[k], j)][V(a, j)], summed by np_sum_row.
 // ---------------------------------------------------------------------------------------
 template <int N>
@@ -2145,7 +2176,7 @@ hipError_t launch_fear(const Env *env, const gw::Params &p0, hipStream_t s, cons
             gw_launch((gw::fear_rows_kernel<N, KMAX, WIDE>), dim3(nfear + nrx * (unsigned)a->K), dim3(128),
                       std::max(dyn, sizeof(float4) * 2 * 64 * 4), s, p, *a, nfear, nrx);
         } else {
-            gw_launch((gw::fear_v2<N, KMAX, WIDE>), dim3(nfear), dim3(gw::V2Cfg<N, KMAX, true, WIDE>::THREADS), dyn,
+            gw_launch((gw::fear_v2<N, KMAX, WIDE>), dim3(nfear), dim3(WIDE ? GW_FEAR_T : 128), dyn,
                       s, p);
         }
         return hipGetLastError();

@@ -51,7 +51,7 @@ def patch(src: str) -> str:
     fear = ins(fear, "    // ---- C ----\n", "    " + fstamp.format(slot=3))
     fear = ins(fear, "        ct.v[5] = np_sum_small(shaped, K);\n    }\n", "    " + fstamp.format(slot=4))
     fear = ins(fear, "    block_stats<T>(p, ct, sh.red, tid, p.stats_row0 + e0 / BE);\n", "    " + fstamp.format(slot=5))
-    fear = ins(fear, "        fear_plan<N, KMAX>(p, sh, tid, pos, act, 0);\n", "        " + fstamp.format(slot=6), after=False)
+    fear = ins(fear, "        fear_plan_actor<N, KMAX>(p, sh, el, ka, pos, act, mdr_k, 0);\n", "        " + fstamp.format(slot=6), after=False)
     src = src[:a] + step + mid + fear + tail
     src += ('\nextern "C" int gw_phase_read(unsigned long long *step, unsigned long long *fear, int n) {\n'
             '    if (hipMemcpyFromSymbol(step, HIP_SYMBOL(gw::gw_phase_clk), sizeof(unsigned long long) * 8 * n) != hipSuccess) return -1;\n'
