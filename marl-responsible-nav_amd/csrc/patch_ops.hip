@@ -357,13 +357,21 @@ __global__ void __launch_bounds__(THREADS) window_kernel(gw::PatchArgs a, unsign
             if (pw >= 0) a.patch[((int64_t)k * a.E + e0 + el) * PP + pw] = s_pv[slot * np + i];
         }
     } else if (a.patch) {  // one thread per element (consecutive lanes: consecutive floats), overrides in registers
-        // i / PP and c / P as multiply-highs (i < PB * PP; P >= 2)
+        // i / PP and c / P as multiply-highs (i < PB * PP; P >= 2).  With m = ceil(2^32 / d) = (2^32 + r) / d
+        // the product overshoots n / d by n r / (d 2^32) < 1: exact while n r < 2^32, which holds for c / P
+        // (c < PP <= 16641) but not for i / PP at the window sizes only this writer takes (PP >= 9604: the
+        // last cells of a 32-env block came out as env el + 1, cell -1), so that quotient is corrected by
+        // the one it can be off by
         const uint32_t m_pp = (uint32_t)((0x100000000ull + (uint64_t)PP - 1) / (uint64_t)PP);
         const uint32_t m_p = (uint32_t)((0x100000000ull + (uint64_t)P - 1) / (uint64_t)P);
         for (int k = 0; k < K; ++k) {
             float *o = a.patch + ((int64_t)k * a.E + e0) * PP;
             for (int i = tid; i < nenv * PP; i += THREADS) {
-                const int el = (int)__umulhi((uint32_t)i, m_pp), c = i - el * PP;
+                int el = (int)__umulhi((uint32_t)i, m_pp), c = i - el * PP;
+                if (c < 0) {
+                    --el;
+                    c += PP;
+                }
                 if (!(s_flag[el] & D_WRITE)) continue;
                 const int slot = el * K + k;
                 const int ctr = s_ctr[slot];
