@@ -163,7 +163,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * GW_SPAN_FEAR_ALT the per-action FeAR table's kernel (fear_alt_kernel, gw_set_fear_alt),
  * GW_SPAN_FEAL the per-agent FeAL kernel (feal_kernel, gw_set_feal),
  * GW_SPAN_FEAR_FULL the N x N responsibility matrix's kernel (fear_full_kernel, gw_set_fear_full),
- * GW_SPAN_FEAR_PREVIEW the two launches of gw_fear_preview (preview_rec_kernel, fear_alt_kernel).
+ * GW_SPAN_FEAR_PREVIEW the two launches of gw_fear_preview (preview_rec_kernel, fear_alt_kernel),
+ * GW_SPAN_FEAR_SHIELD the two launches of gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -171,7 +172,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
 enum {
     GW_SPAN_STEP = 0, GW_SPAN_OBS = 1, GW_SPAN_FEAR = 2, GW_SPAN_ACT = 3, GW_SPAN_CNN_L1 = 4,
     GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8,
-    GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11, GW_SPAN_FEAR_PREVIEW = 12
+    GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11, GW_SPAN_FEAR_PREVIEW = 12,
+    GW_SPAN_FEAR_SHIELD = 13 /* the two launches of one gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel) */
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -408,6 +410,58 @@ gw_status gw_dims(void *env, int64_t out[5]);
 const char *gw_last_error(void);
 
 void gw_destroy(void *env);
+
+/* The coordinated responsibility shield: gw_fear_preview and gw_fear_shield (include/rollout_ops.h) composed
+ * over the RL agents one after the other, in one call, and the table of the joint action that will actually be
+ * applied.  gw_fear_shield is unilateral: each agent's row assumes that the others keep their proposed actions,
+ * so with several agents shielded at once its promise fails exactly in the envs where somebody else was
+ * replaced.  Here every visit sees the actions the agents before it have fixed.  Per env, with `scripted` the
+ * scripted agents' actions and prop[k] the proposed RL actions (given, or NULL = drawn with the step's own
+ * Philox counters, exactly as gw_fear_preview does):
+ *   cur = prop
+ *   for s in 1..sweeps:
+ *     changed = false
+ *     for k in 0..K-1 ascending, where bit k of `agents` is set:
+ *       t = row k of gw_fear_preview's table for the joint action (cur, scripted)
+ *       r = the pick of csrc/fear_shield.h (gw_fear_shield's rule) on (t, cur[k], mask[k], probs of k, tau)
+ *       stuck[k] = bit 1 of r's flags            (the last visit's answer)
+ *       if r.action != cur[k]: cur[k] = r.action, changed = true
+ *     if not changed: break
+ *   T = gw_fear_preview's table for (cur, scripted)
+ * Outputs: actions_out [E][K] = cur (required; may alias rl_actions); fear_alt [E][K][9] f64 = T, bit for bit
+ * gw_fear_preview's; joint [E][N] = the joint action the step will apply; flags [E][K] u8 (each of the three
+ * may be NULL):
+ *   bit 0  cur[k] != prop[k];
+ *   bit 1  stuck[k]: the agent's last visit found no allowed action;
+ *   bit 2  "over": agent k is shielded and T[k][cur[k]] > tau (f64 compare): the promise does not hold here;
+ *   bit 3  "unconverged": the last sweep that ran changed something; set on all K entries of the env.
+ * An agent whose current action is still allowed keeps it; an unshielded agent is never visited and its flags are
+ * 0 apart from bit 3; agents == 0 sets nothing.  A proposed action outside 0..8 is read as 0 (stay), which is
+ * what gw_step and gw_fear_preview apply for it: prop, actions_out and bit 0 all speak of that 0.
+ * It follows that
+ *   - T[e][k][actions_out[e][k]] is bit for bit the fear[e][k] of the gw_step that applies actions_out (and the
+ *     same scripted actions), for every k, shielded or not;
+ *   - where bit 2 is clear, that step's fear[e][k] <= tau;
+ *   - in an env with bit 3 clear every shielded agent with bit 1 clear and a non-zero mask has bit 2 clear (the
+ *     unchanged sweep saw the final joint action; an agent whose mask is 0 is kept whatever its FeAR, flags 0);
+ *   - sweeps = 1, agents = 1 << k gives gw_fear_shield's actions_out and flag bits 0-1 for that k.
+ * mask [E][K] u16 9-bit action masks (NULL: all nine), probs [K][E][9] f32 in the replay ring's layout (NULL:
+ * none), agents: bit k = RL agent k is shielded, sweeps in 1..GW_SHIELD_MAX_SWEEPS.
+ * Conventions of gw_fear_preview: works on cfg.fear == 0 envs; changes no env state, step output, pipeline state
+ * or obs-destination table; shares the preview's record buffer (a first call of either while `stream` captures
+ * returns GW_ERR_STATE, later calls can be captured); no host synchronisation; GW_ERR_STATE before the first
+ * gw_reset; GW_ERR_ARG on a null env, null actions_out or sweeps out of range.
+ * Cost: two launches on `stream` (preview_rec_kernel, then fear_shield_joint_kernel: one wave per env, every
+ * visit and the final table in it), one GW_SPAN_FEAR_SHIELD span while profiling.  A visit of agent k runs its
+ * 9 (1 + 8 (c_k - 1)) world updates (close count c_k); the final table runs those of all K agents, or, when
+ * the last sweep changed nothing, only those of the unshielded ones (the shielded agents' rows are then the
+ * visits').  gw_count_sims counts them all.  The composed form costs sweeps x K previews (K rows each) and
+ * sweeps x K shield launches plus one preview. */
+#define GW_SHIELD_MAX_SWEEPS 8
+gw_status gw_fear_shield_joint(void *env, const int32_t *rl_actions, const int32_t *scripted,
+                               const uint16_t *mask, const float *probs, double tau, uint32_t agents,
+                               int32_t sweeps, int32_t *actions_out, uint8_t *flags, double *fear_alt,
+                               int32_t *joint, void *stream);
 
 #ifdef __cplusplus
 }

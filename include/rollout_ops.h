@@ -155,6 +155,8 @@ gw_status gw_feal_accum(const double *feal, const uint8_t *active, int64_t E, in
  * one agent alone is shielded (agents = 1 << k), the following step's fear[e][k] is exactly the chosen
  * entry t[actions_out[e][k]], hence <= tau wherever flag bit 1 is clear.  With several agents shielded
  * at once that holds for an agent only in the envs where every other agent's action was kept.
+ * gw_fear_shield_joint (include/gridenv.h) is the coordinated form: it visits the agents one after the other
+ * and returns the table of the joint action that is applied.
  * One launch, one thread per (env, agent), deterministic, graph-capturable, no host sync. */
 gw_status gw_fear_shield(const double *fear_alt, const int32_t *actions_in, const uint16_t *mask,
                          const float *probs, int64_t E, int32_t K, double tau, uint32_t agents,

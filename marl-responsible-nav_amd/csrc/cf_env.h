@@ -522,4 +522,23 @@ hipError_t launch_fear_full(int N, dim3 grid, dim3 block, size_t dyn, hipStream_
 // ([E][N] or null)
 hipError_t launch_preview_rec(int N, hipStream_t s, const Params &p, int32_t *actions, int32_t *mdr);
 
+// gw_fear_shield_joint's arguments beside the env's (include/gridenv.h): mask [E][K] or null, probs [K][E][9] or
+// null, agents / sweeps already checked, actions_out [E][K], flags [E][K] / table [E][K][9] / joint [E][N] or null
+struct ShieldJointArgs {
+    const uint16_t *mask;
+    const float *probs;
+    double tau;
+    uint32_t agents;
+    int sweeps;
+    int32_t *actions_out;
+    uint8_t *flags;
+    double *table;
+    int32_t *joint;
+};
+
+// fear_shield_joint_kernel<N> (fear_shield_joint.hip, gw_fear_shield_joint) over p's env range on s, through
+// gwprof::launch, from the record in p.fwork
+hipError_t launch_fear_shield_joint(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
+                                    const ShieldJointArgs &a);
+
 }  // namespace gw

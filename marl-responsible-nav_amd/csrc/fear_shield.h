@@ -15,6 +15,8 @@
 // The shield is unilateral: the row assumes that the OTHER agents play their proposed actions.  When one
 // agent alone is shielded the step's fear of that agent is exactly the chosen entry t[pick]; with several
 // agents shielded at once that holds for an agent only if the others' actions were kept.
+// gw_fear_shield_joint (csrc/fear_shield_joint.hip, include/gridenv.h) runs this same pick agent after agent,
+// each on the row of the actions fixed so far, and hands back the table of the applied joint action.
 #ifndef FEAR_SHIELD_H
 #define FEAR_SHIELD_H
 #include <stdint.h>

@@ -40,45 +40,9 @@
 #include "fear_alt_tasks.h"
 #include "resp_tables.h"
 #include "cf_env.h"
+#include "np_sum.h"  // np_sum_row (shared with fear_shield_joint.hip)
 
 namespace gw {
-
-// numpy float64 sum (0.0 + pairwise_sum) of an N*N matrix whose only non-zero row is `row`
-// (np.sum(FeAR_vals), custom/ma_customenv.py:252).  Zeros never change a partial sum here
-// (no -0.0 can occur), so only the row's terms are accumulated, in numpy's order.
-template <int N>
-__device__ __forceinline__ double np_sum_row(const double (&v)[N], int row) {
-    constexpr int n = N * N;
-    if (n < 8) {
-        double res = 0.0;
-#pragma unroll
-        for (int j = 0; j < N; ++j) res = __dadd_rn(res, v[j]);
-        return __dadd_rn(0.0, res);
-    } else {
-        static_assert(N * N <= 128, "N <= 11");
-        double r[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) r[q] = 0.0;
-        constexpr int main_end = n - (n % 8);
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const int idx = row * N + j;
-            if (idx < main_end) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    if ((idx & 7) == q) r[q] = __dadd_rn(r[q], v[j]);
-            }
-        }
-        double res = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                               __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const int idx = row * N + j;
-            if (idx >= main_end) res = __dadd_rn(res, v[j]);
-        }
-        return __dadd_rn(0.0, res);
-    }
-}
 
 // numpy sum of a short 1-D f64 vector (n <= 8): scores += np.sum(rewards) (agent.py:173).
 __device__ __forceinline__ double np_sum_small(const double (&a)[MAXN], int n) {
@@ -3141,6 +3105,17 @@ gw_status gw_set_fear_full(void *handle, double *resp_full, uint16_t *resp_valid
     return GW_OK;
 }
 
+// the record buffer gw_fear_preview and gw_fear_shield_joint share, allocated by the first call of either
+static gw_status ensure_preview_rec(Env *env, hipStream_t s, const char *who) {
+    if (env->preview_rec) return GW_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;  // hipMalloc is not allowed while the stream captures
+    HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return fail(GW_ERR_STATE, (std::string(who) + ": the first call allocates the record buffer and cannot run "
+                                   "while the stream is capturing; call it once before the capture").c_str());
+    return dalloc(env, &env->preview_rec, (size_t)env->E * (env->N <= 4 ? 1 : 2));
+}
+
 gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,
                           int32_t *actions, int32_t *mdr, void *stream) {
     Env *env = static_cast<Env *>(handle);
@@ -3148,14 +3123,7 @@ gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t
     if (!fear_alt) return fail(GW_ERR_ARG, "gw_fear_preview: null table");
     if (!env->initialized) return fail(GW_ERR_STATE, "gw_fear_preview before gw_reset");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!env->preview_rec) {  // hipMalloc is not allowed while the stream captures
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_TRY(hipStreamIsCapturing(s, &cs));
-        if (cs != hipStreamCaptureStatusNone)
-            return fail(GW_ERR_STATE, "gw_fear_preview: the first call allocates the record buffer and cannot run "
-                                      "while the stream is capturing; call it once before the capture");
-        GW_TRY(dalloc(env, &env->preview_rec, (size_t)env->E * (env->N <= 4 ? 1 : 2)));
-    }
+    GW_TRY(ensure_preview_rec(env, s, "gw_fear_preview"));
     // the env's state as the next gw_step will read it: every path orders the last world update before the
     // caller's later work on its stream.  No step output, no descriptor, no pipeline state is touched
     gw::Params p = make_params(env);
@@ -3169,6 +3137,35 @@ gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t
         rec = gw::launch_preview_rec(env->N, s, q, actions, mdr);
         if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
         gw_launch((gw::fear_alt_kernel<decltype(n)::value>), grid, block, dyn, s, q, fear_alt);
+    }));
+    HIP_TRY(rec);
+    return GW_OK;
+}
+
+gw_status gw_fear_shield_joint(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                               const float *probs, double tau, uint32_t agents, int32_t sweeps, int32_t *actions_out,
+                               uint8_t *flags, double *fear_alt, int32_t *joint, void *stream) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_fear_shield_joint: null env");
+    if (!actions_out) return fail(GW_ERR_ARG, "gw_fear_shield_joint: null actions_out");
+    if (sweeps < 1 || sweeps > GW_SHIELD_MAX_SWEEPS)
+        return fail(GW_ERR_ARG, "gw_fear_shield_joint: sweeps outside 1..GW_SHIELD_MAX_SWEEPS");
+    if (!env->initialized) return fail(GW_ERR_STATE, "gw_fear_shield_joint before gw_reset");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GW_TRY(ensure_preview_rec(env, s, "gw_fear_shield_joint"));
+    // as gw_fear_preview: the env's state as the next gw_step will read it, nothing of the env written
+    gw::Params p = make_params(env);
+    p.rl = rl_actions;
+    p.scripted = scripted;
+    p.fwork = env->preview_rec;
+    const gw::ShieldJointArgs a{mask, probs, tau, agents, sweeps, actions_out, flags, fear_alt, joint};
+    hipError_t rec = hipSuccess;
+    GW_TRY(launch_cf(env, GW_SPAN_FEAR_SHIELD, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        // the record of the proposed joint action, then the sweeps and the final table on it (fear_shield_joint.hip,
+        // its own code object): both launches are the one span
+        rec = gw::launch_preview_rec(env->N, s, q, nullptr, nullptr);
+        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
+        rec = gw::launch_fear_shield_joint(env->N, grid, block, dyn, s, q, a);
     }));
     HIP_TRY(rec);
     return GW_OK;

@@ -35,6 +35,12 @@ def main(argv=None):
                     help="responsibility shield: before every step, replace an RL action whose previewed FeAR "
                          "exceeds TAU by an allowed one (the most probable under the actor); also prints how many "
                          "agent-steps were replaced / had no allowed action")
+    ap.add_argument("--shield-mode", choices=["unilateral", "joint"], default="unilateral",
+                    help="unilateral: every agent's choice assumes that the others keep their proposed actions; "
+                         "joint: the agents are visited one after the other, each on the actions fixed so far, and "
+                         "the agent-steps whose applied action still exceeds TAU are printed too")
+    ap.add_argument("--shield-sweeps", type=int, default=2, metavar="N",
+                    help="joint mode: at most N sweeps over the agents (1..8; a sweep that changes nothing ends them)")
     args = ap.parse_args(argv)
 
     from marlnav import scenario as S
@@ -54,7 +60,8 @@ def main(argv=None):
         m.load(args.checkpoint)
         actors = m.actors
     r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps, fear=args.feal or args.resp_full,
-                 seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield)
+                 seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield,
+                 shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
@@ -62,6 +69,9 @@ def main(argv=None):
     if args.shield is not None:
         print(f"Shield (tau = {args.shield:g}): replaced {r['shield_replaced'].tolist()}, "
               f"no allowed action {r['shield_stuck'].tolist()} agent-steps per RL agent")
+        if args.shield_mode == "joint":
+            print(f"Joint shield ({args.shield_sweeps} sweeps): over tau {r['shield_over'].tolist()} agent-steps per RL "
+                  f"agent, {r['shield_unconverged']} env-steps unconverged")
     if args.feal:
         print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
     if args.resp_full:

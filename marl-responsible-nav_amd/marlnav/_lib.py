@@ -26,7 +26,8 @@ LIB_PATH = os.path.join(CSRC, "libgridenv_measure.so" if MEASURE else "libgriden
 HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_ops.hip"),
                os.path.join(CSRC, "actor_ops.hip"), os.path.join(CSRC, "rollout_ops.hip"),
                os.path.join(CSRC, "maddpg_ops.hip"), os.path.join(CSRC, "patch_ops.hip"),
-               os.path.join(CSRC, "fear_full.hip"), os.path.join(CSRC, "fear_preview.hip")]
+               os.path.join(CSRC, "fear_full.hip"), os.path.join(CSRC, "fear_preview.hip"),
+               os.path.join(CSRC, "fear_shield_joint.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
@@ -34,7 +35,8 @@ SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.jo
                                    os.path.join(CSRC, "fear_alt_tasks.h"), os.path.join(CSRC, "dispatch.h"),
                                    os.path.join(CSRC, "obs_value.h"), os.path.join(CSRC, "obs_dest.h"),
                                    os.path.join(CSRC, "resp_tables.h"), os.path.join(CSRC, "cf_env.h"),
-                                   os.path.join(CSRC, "draw_action.h"), os.path.join(CSRC, "fear_shield.h")]
+                                   os.path.join(CSRC, "draw_action.h"), os.path.join(CSRC, "fear_shield.h"),
+                                   os.path.join(CSRC, "np_sum.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -195,7 +197,8 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
            "gw_set_fear_alt", "gw_fear_regret_accum",
            "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts",
-           "gw_set_feal", "gw_feal_accum", "gw_set_fear_full", "gw_fear_preview", "gw_fear_shield"]
+           "gw_set_feal", "gw_feal_accum", "gw_set_fear_full", "gw_fear_preview", "gw_fear_shield",
+           "gw_fear_shield_joint"]
 
 
 class GwObsSource(C.Structure):
@@ -357,6 +360,8 @@ def _declare(L):
     L.gw_fear_preview.restype = C.c_int
     L.gw_fear_shield.argtypes = [p, p, p, p, C.c_int64, C.c_int32, C.c_double, C.c_uint32, p, p, p]
     L.gw_fear_shield.restype = C.c_int
+    L.gw_fear_shield_joint.argtypes = [p, p, p, p, p, C.c_double, C.c_uint32, C.c_int32, p, p, p, p, p]
+    L.gw_fear_shield_joint.restype = C.c_int
     L.gw_affine_relu_fwd.argtypes = [p, p, p, p, C.c_int32, C.c_int64, C.c_int32, p]
     L.gw_affine_relu_fwd.restype = C.c_int
     L.gw_affine_relu_bwd.argtypes = [p] * 7 + [C.c_int32, C.c_int64, C.c_int32, p]

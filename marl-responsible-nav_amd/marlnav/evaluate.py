@@ -30,7 +30,8 @@ from .vec_env import VecGridEnv
 def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, max_steps: int = 150,
              fear: bool = False, seed: int = 42, record_actions: bool = False, fused: bool | None = None,
              variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False,
-             feal: bool = False, resp_full: bool = False, shield: float | None = None) -> dict:
+             feal: bool = False, resp_full: bool = False, shield: float | None = None,
+             shield_mode: str = "unilateral", shield_sweeps: int = 2) -> dict:
     """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
     matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
     restricted agent j) summed over the episodes still running and divided by "steps".
@@ -49,7 +50,15 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
     probabilities, every RL agent shielded), then ``env.step`` with the shielded actions; works with
     ``fear=False`` (the reference's evaluation configuration).  The result also carries "shield_replaced" [K]
     and "shield_stuck" [K] (int64 CPU tensors): the agent-steps of the episodes still running whose action
-    was replaced / that had no allowed action.  Recorded actions are the ones applied."""
+    was replaced / that had no allowed action.  Recorded actions are the ones applied.
+    shield_mode: "unilateral" (the default, the two calls above) or "joint": the one call
+    ``env.fear_shield_joint`` with at most ``shield_sweeps`` sweeps (the agents visited one after the other, each
+    on the actions fixed so far).  The result then also carries "shield_over" [K] (the agent-steps, counted as
+    the other two, whose applied action's FeAR exceeds tau: flag bit 2) and "shield_unconverged" (the env-steps
+    whose last sweep still changed an action: flag bit 3)."""
+    if shield_mode not in ("unilateral", "joint"):
+        raise ValueError('evaluate(shield_mode=...): "unilateral" or "joint"')
+    joint_mode = shield is not None and shield_mode == "joint"
     if fear_regret and not fear:
         raise ValueError("evaluate(fear_regret=True) needs fear=True")
     if feal and not fear:
@@ -79,7 +88,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         full = torch.zeros((env.N, env.N), dtype=torch.float64, device=dev) if resp_full else None
         full_calls = torch.zeros((), dtype=torch.int64, device=dev)
         table = torch.empty((episodes, env.K, 9), dtype=torch.float64, device=dev) if shield is not None else None
-        shield_cnt = torch.zeros((2, env.K), dtype=torch.int64, device=dev)  # replaced, stuck
+        # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
+        shield_cnt = torch.zeros((4 if joint_mode else 2, env.K), dtype=torch.int64, device=dev)
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):
@@ -87,7 +97,13 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
                 actions, probs = actors.act_env(env, env.out["mask"], training=False)
             else:
                 actions, probs = actors.act(env.out["obs"], env.out["mask"], training=False)
-            if shield is not None:  # actor -> preview -> shield -> step; the episodes still running are counted
+            if joint_mode:  # actor -> the coordinated shield (one call) -> step
+                actions, flags, _ = env.fear_shield_joint(actions, None, mask=env.out["mask"], probs=probs.contiguous(),
+                                                          tau=float(shield), sweeps=shield_sweeps, table=table)
+                on = active.to(torch.int64).unsqueeze(1)
+                for b in range(4):
+                    shield_cnt[b] += (((flags >> b) & 1) * on).sum(0)
+            elif shield is not None:  # actor -> preview -> shield -> step; the episodes still running are counted
                 env.fear_preview(actions, out=table)
                 actions, flags = env.fear_shield(table, actions, mask=env.out["mask"], probs=probs.contiguous(),
                                                  tau=float(shield))
@@ -138,6 +154,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             out["resp_full"], out["resp_full_steps"] = full.cpu(), int(full_calls)
         if shield is not None:
             out["shield_replaced"], out["shield_stuck"] = shield_cnt[0].cpu(), shield_cnt[1].cpu()
+            if joint_mode:
+                out["shield_over"], out["shield_unconverged"] = shield_cnt[2].cpu(), int(shield_cnt[3, 0])
         if record_actions:
             # the early-stop check runs every 8 steps: keep the actions up to the first step after
             # which every episode had ended (the steps an env-at-a-time loop would have taken)

@@ -181,7 +181,7 @@ class Rollout:
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
                  patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False,
                  fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
-                 shield: float | None = None):
+                 shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -225,7 +225,12 @@ class Rollout:
         actor's probabilities, every RL agent shielded), then ``env.step`` with the shielded actions.  The ring
         keeps the actor's probabilities unchanged (the reference stores ``cont_actions``).  ``shield_flags``
         holds the last step's [E, K] flags and ``totals()`` carries "shield_replaced" [K] and "shield_stuck"
-        [K].  Eager only: ``capture`` raises ValueError.  Works with FeAR off (``fear=False``) too."""
+        [K].  Eager only: ``capture`` raises ValueError.  Works with FeAR off (``fear=False``) too.
+        shield_mode: "unilateral" (the default: the two calls above, each agent's row assuming that the others
+        keep their proposed actions) or "joint": the one call ``env.fear_shield_joint`` (the agents visited one
+        after the other, at most ``shield_sweeps`` sweeps); ``shield_table`` then holds the [E, K, 9] FeAR table
+        of the joint action the step applies, ``shield_flags`` carries bits 2 (over tau) and 3 (unconverged)
+        too, and ``totals()`` also carries "shield_over" [K] and "shield_unconverged"."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -311,16 +316,32 @@ class Rollout:
         self.shield = None if shield is None else float(shield)
         self.shield_flags = None  # the last step's [E, K] uint8 flags (VecGridEnv.fear_shield)
         self._shield_cnt = None
+        if shield_mode not in ("unilateral", "joint"):
+            raise ValueError('Rollout(shield_mode=...): "unilateral" or "joint"')
+        self.shield_mode, self.shield_sweeps = shield_mode, int(shield_sweeps)
+        self.shield_table = None  # joint mode: the last step's [E, K, 9] table of the applied joint action
         if self.shield is not None:
-            self._shield_cnt = torch.zeros((2, env.K), dtype=torch.int64, device=env.device)  # replaced, stuck
+            # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
+            self._shield_cnt = torch.zeros((4 if shield_mode == "joint" else 2, env.K), dtype=torch.int64,
+                                           device=env.device)
             self._shield_table = torch.empty((env.E, env.K, 9), dtype=torch.float64, device=env.device)
-            self._shield_joint = torch.empty((env.E, env.N), dtype=torch.int32, device=env.device)
             self._shield_out = torch.empty((env.E, env.K), dtype=torch.int32, device=env.device)
             self.shield_flags = torch.zeros((env.E, env.K), dtype=torch.uint8, device=env.device)
+            if shield_mode == "joint":
+                self.shield_table = self._shield_table
+            else:  # the preview's joint action: the random policy's proposals are read from it
+                self._shield_joint = torch.empty((env.E, env.N), dtype=torch.int32, device=env.device)
 
     def _shielded(self, actions, probs, mask):
         """actor -> preview -> shield: the actions the step will apply, and the flags into the totals."""
         env = self.env
+        if self.shield_mode == "joint":  # the one call; None actions: the draws the step would make
+            out, flags, _ = env.fear_shield_joint(actions, None, mask=mask, probs=probs, tau=self.shield,
+                                                  sweeps=self.shield_sweeps, out=self._shield_out,
+                                                  flags=self.shield_flags, table=self._shield_table)
+            for b in range(4):
+                self._shield_cnt[b] += ((flags >> b) & 1).sum(0)
+            return out
         if actions is None:  # the device-random policy: the preview reports the actions the step would draw
             env.fear_preview(None, out=self._shield_table, actions=self._shield_joint)
             actions = self._shield_joint[:, :env.K].contiguous()
@@ -652,7 +673,9 @@ class Rollout:
         (f64 CPU tensor, all-reduced with the rest), and "resp_full_steps", this rank's steps (like
         "resp_steps": the ranks step in lockstep, so the count is not summed over them).
         With ``shield``: "shield_replaced" [K] and "shield_stuck" [K] (int64 CPU tensors): the agent-steps whose
-        action the shield replaced (flag bit 0) / that had no allowed action (flag bit 1).
+        action the shield replaced (flag bit 0) / that had no allowed action (flag bit 1).  With
+        ``shield_mode="joint"`` also "shield_over" [K] (agent-steps whose applied action's FeAR exceeds tau, flag
+        bit 2) and "shield_unconverged" (env-steps whose last sweep still changed an action, flag bit 3).
         With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
         the responsibility total): every rank calls it."""
         if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
@@ -663,6 +686,8 @@ class Rollout:
             if self.distributed:
                 dist.all_reduce(cnt, group=self.group)
             shield = {"shield_replaced": cnt[0].cpu(), "shield_stuck": cnt[1].cpu()}
+            if self.shield_mode == "joint":
+                shield["shield_over"], shield["shield_unconverged"] = cnt[2].cpu(), int(cnt[3, 0])
             if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
                     and self._full is None):
                 self._flush()

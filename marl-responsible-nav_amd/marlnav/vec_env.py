@@ -579,6 +579,46 @@ class VecGridEnv:
                                                _ptr(out), _ptr(flags), self._stream()), "gw_fear_shield")
         return out, flags
 
+    def fear_shield_joint(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
+                          mask: torch.Tensor | None = None, probs: torch.Tensor | None = None, tau: float = 0.0,
+                          agents: int | None = None, sweeps: int = 2, out: torch.Tensor | None = None,
+                          flags: torch.Tensor | None = None, table: torch.Tensor | None = None,
+                          joint: torch.Tensor | None = None):
+        """The coordinated responsibility shield (gw_fear_shield_joint): -> (actions [E, K] int32, flags [E, K]
+        uint8, table [E, K, 9] float64).  ``fear_preview`` + ``fear_shield`` composed over the shielded RL
+        agents one after the other (ascending k, each visit on the table of the actions fixed so far), at most
+        ``sweeps`` times round or until a sweep changes nothing, in one call; ``table`` is ``fear_preview`` of
+        the joint action that ``step(actions, scripted)`` will apply, so ``table[e, k, actions[e, k]]`` is that
+        step's ``fear[e, k]`` bit for bit.  flags: bit 0 replaced, bit 1 the last visit found no allowed action,
+        bit 2 the agent is shielded and its entry exceeds tau, bit 3 the env's last sweep still changed
+        something.  rl_actions / scripted as for ``fear_preview`` (None: the draws the step will make); mask,
+        probs, tau, agents as for ``fear_shield``; out may be ``rl_actions`` itself; joint: optional [E, N]
+        int32 output, the joint action of that step.  Changes no env state; works with ``fear=False``."""
+        E, K, N = self.E, self.K, self.N
+        rl = self._as_i32(rl_actions, (E, K))
+        sa = self._as_i32(scripted, (E, N - K))
+        if not 1 <= int(sweeps) <= 8:
+            raise ValueError("fear_shield_joint(sweeps=...): 1..8 (GW_SHIELD_MAX_SWEEPS)")
+        if out is None:
+            out = torch.empty((E, K), dtype=torch.int32, device=self.device)
+        if flags is None:
+            flags = torch.empty((E, K), dtype=torch.uint8, device=self.device)
+        if table is None:
+            table = torch.empty((E, K, 9), dtype=torch.float64, device=self.device)
+        for t, dt, n, name in ((table, torch.float64, E * K * 9, "table"), (mask, torch.int16, E * K, "mask"),
+                               (probs, torch.float32, K * E * 9, "probs"), (out, torch.int32, E * K, "out"),
+                               (flags, torch.uint8, E * K, "flags"), (joint, torch.int32, E * N, "joint")):
+            if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"fear_shield_joint({name}=...): need a contiguous {dt} tensor of {n} elements on "
+                                 f"{self.device}")
+        bits = (1 << K) - 1 if agents is None else int(agents) & 0xFFFFFFFF
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_fear_shield_joint(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), _ptr(probs),
+                                                     float(tau), bits, int(sweeps), _ptr(out), _ptr(flags),
+                                                     _ptr(table), _ptr(joint), self._stream()),
+                       "gw_fear_shield_joint")
+        return out, flags, table
+
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
         """Egocentric local observations (gw_obs_patch): [K, E, size, size] float32, agent k's obs

@@ -8,6 +8,9 @@ preview launches' busy time from the per-launch profiling spans (GW_SPAN_FEAR_PR
 updates per step from gw_count_sims.  One JSON line:
 
     python tools/bench_fear_preview.py [--steps 300] [--warmup 50] [--envs 65536] [--scenario grid32]
+
+--mode joint [--sweeps N] [--repeats 5]: the coordinated shield (gw_fear_shield_joint) against the same rule
+composed from the two entry points above, on one fixed world in the same run (joint_mode below).
 """
 import argparse
 import json
@@ -54,8 +57,69 @@ def timed(fn, n):
     return ev0.elapsed_time(ev1) * 1e3 / n
 
 
+def joint_mode(env, args):
+    """--mode joint: on one fixed world (the env after the warm-up steps, the random policy's proposals, the env's
+    action mask, every RL agent shielded) time, in this same run, (a) the rule of gw_fear_shield_joint composed
+    from gw_fear_preview + gw_fear_shield(agents = 1 << k) with one sweep: K previews, K shields and the final
+    preview (two launches per preview); (b) the one joint call at sweeps = 1, 2, 4 (and --sweeps); (c) the share of envs
+    with flag bits 0, 2 and 3.  Each figure: `repeats` runs of `steps` calls between two HIP events after a
+    warm-up; median, min and max over the runs in us per call."""
+    import statistics
+    E, K, N, dev = env.E, env.K, env.N, env.device
+    table = torch.empty((E, K, 9), dtype=torch.float64, device=dev)
+    joint = torch.empty((E, N), dtype=torch.int32, device=dev)
+    env.obs_fence()
+    env.fear_preview(None, out=table, actions=joint)
+    prop = joint[:, :K].contiguous()
+    scripted = joint[:, K:].contiguous()
+    mask = env.out["mask"]
+    cur = torch.empty_like(prop)
+    flags = torch.zeros((E, K), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(prop)
+
+    def composed():
+        cur.copy_(prop)
+        for k in range(K):
+            env.fear_preview(cur, scripted, out=table)
+            env.fear_shield(table, cur, mask=mask, tau=args.tau, agents=1 << k, out=cur, flags=flags)
+        env.fear_preview(cur, scripted, out=table)
+
+    def joint_call(sweeps):
+        return lambda: env.fear_shield_joint(prop, scripted, mask=mask, tau=args.tau, sweeps=sweeps, out=out,
+                                             flags=flags, table=table)
+
+    def spread(fn):
+        for _ in range(args.warmup):
+            fn()
+        runs = sorted(timed(fn, args.steps) for _ in range(args.repeats))
+        return {"median_us": statistics.median(runs), "min_us": runs[0], "max_us": runs[-1], "runs": len(runs)}
+
+    res = {"composed_one_sweep": spread(composed)}
+    composed()
+    torch.cuda.synchronize()
+    want_actions, want_table = cur.clone(), table.clone()
+    for sweeps in sorted({1, 2, 4, args.sweeps}):
+        res[f"joint_sweeps_{sweeps}"] = spread(joint_call(sweeps))
+        torch.cuda.synchronize()
+        share = lambda b: float(((flags >> b) & 1).any(1).float().mean())  # noqa: E731
+        res[f"joint_sweeps_{sweeps}"].update(share_replaced=share(0), share_over=share(2), share_unconverged=share(3))
+        if sweeps == 1:  # the same rule: the same answer
+            assert torch.equal(out, want_actions) and torch.equal(table, want_table)
+    res["composed_again"] = spread(composed)
+    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+    env.count_sims(ctr)
+    joint_call(args.sweeps)()
+    env.count_sims(None)
+    torch.cuda.synchronize()
+    res["joint_sims_per_call"] = int(ctr.item())
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["unilateral", "joint"], default="unilateral")
+    ap.add_argument("--sweeps", type=int, default=2, help="--mode joint: the sweep count timed beside 1, 2 and 4")
+    ap.add_argument("--repeats", type=int, default=5, help="--mode joint: timed runs per figure")
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs", type=int, default=65536)
@@ -76,6 +140,14 @@ def main(argv=None):
         sh.step()
     for _ in range(args.warmup):
         env.step()
+
+    if args.mode == "joint":
+        res = joint_mode(env, args)
+        env.close()
+        print(json.dumps({"tool": "bench_fear_preview", "mode": "joint", "scenario": args.scenario, "envs": E,
+                          "agents": env.N, "rl_agents": env.K, "tau": args.tau, "calls_per_run": args.steps, **res}),
+              flush=True)
+        return
 
     us = {}
     for name, fn in (("step", env.step), ("shielded", sh.step), ("step_again", env.step)):
