@@ -383,11 +383,27 @@ gw_status gw_set_obs_dtype(void *env, int dtype);
  * Always the full writer, and no entry survives: the merged kernel path, bf16 obs, gw_set_obs_dtype,
  * gw_reset, gw_pipeline_load, gw_graph_replayed (call one of the two after replaying a graph of
  * captured steps, or forget), and steps recorded while the stream is capturing.
- * gw_obs_delta_counts: out[0] / out[1] = gw_steps whose obs the full / the delta writer wrote. */
+ * gw_obs_delta_counts: out[0] / out[1] = gw_steps whose obs the full / the delta writer wrote.
+ *
+ * The ride.  On the defer path with FeAR on (joined, wide blocks), an eager async step
+ * (gw_set_obs_async(env, 1)) whose delta writer covers the whole env range in one launch
+ * (GW_OBS_CHUNKS unset or 1, no final_obs, profiling off, `stream` not capturing) runs that writer
+ * as a block role of the FeAR launch on `stream` itself (fear_delta_kernel): the step is two
+ * launches on the caller's stream and uses no internal stream, event or cross-queue wait.  After
+ * such a step the obs are ordered on `stream` like every other output of the step, and gw_obs_fence
+ * has nothing to wait for (calling it stays correct and cheap; a caller that reads the obs on
+ * another stream orders that stream after `stream`, as for rewards and dones).  Every other step
+ * takes the pipeline above unchanged, and the two forms may alternate from step to step.
+ * gw_set_obs_ride(env, 0) turns the ride off and (env, 1) on again, between any two steps (only 0
+ * or 1, else GW_ERR_ARG; A/B: the results are the same bit for bit); marlnav.VecGridEnv calls it
+ * with GW_OBS_RIDE from the environment when it creates an env.  gw_obs_ride_count: the gw_steps
+ * whose writer rode (each of them counts as a delta write in gw_obs_delta_counts too). */
 #define GW_OBS_DESTS 8
 gw_status gw_set_obs_delta(void *env, int on);
 gw_status gw_obs_dest_forget(void *env, const void *ptr);
 gw_status gw_obs_delta_counts(void *env, int64_t out[2]);
+gw_status gw_set_obs_ride(void *env, int on);
+gw_status gw_obs_ride_count(void *env, int64_t *out);
 
 /* The FeAR kernel's envs per block, before the first gw_reset (it fixes gw_stats_rows: size the
  * stats buffer after it): wide = 1, 0 = narrow (half the envs per block).  The rule for the default:

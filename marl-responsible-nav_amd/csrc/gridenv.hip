@@ -765,22 +765,25 @@ __device__ __forceinline__ void decode_patches(const Params &p, const uint4 &cel
     }
 }
 
-__global__ void __launch_bounds__(DELTA_T) obs_delta_kernel(Params p, float *__restrict__ obs,
-                                                            uint32_t *__restrict__ saved) {
+// the writer's block `bid` (of ceil(envs / (DELTA_T / K))); every thread of the block comes here
+__device__ __forceinline__ void obs_delta_block(const Params &p, float *__restrict__ obs,
+                                                uint32_t *__restrict__ saved, uint32_t bid) {
     const int K = p.K, HW = p.HW;
     const int eb = DELTA_T / K;  // envs per block
     const int el = threadIdx.x / K, k = threadIdx.x - el * K;
-    const int64_t e = p.e_begin + (int64_t)blockIdx.x * eb + el;
+    const int64_t e = p.e_begin + (int64_t)bid * eb + el;
     const bool live = el < eb && e < p.e_end;
-    uint4 nw[3], ocells;
+    // (named registers, not an array: as a block role beside fear_block an array part-filled under
+    // `live` stayed in scratch)
+    uint4 n0 = make_uint4(0u, 0u, 0u, 0u), n1 = n0, n2 = n0, ocells = n0;
     uint32_t nf = 0, of = 0;
     if (live) {
         const uint4 *dn = reinterpret_cast<const uint4 *>(p.desc + e * NDESC);
         const uint4 *ds = reinterpret_cast<const uint4 *>(saved + e * NDESC);
-        nw[0] = dn[0];
-        nw[1] = dn[1];
-        nw[2] = dn[2];
-        nf = nw[1].x;
+        n0 = dn[0];
+        n1 = dn[1];
+        n2 = dn[2];
+        nf = n1.x;
         ocells = ds[0];
         of = saved[e * NDESC + 4];
     }
@@ -788,12 +791,12 @@ __global__ void __launch_bounds__(DELTA_T) obs_delta_kernel(Params p, float *__r
     if (!live || !(nf & D_WRITE)) return;  // not written this step: the buffer and `saved` stay
     if (k == 0) {
         uint4 *ds = reinterpret_cast<uint4 *>(saved + e * NDESC);
-        ds[0] = nw[0];
-        ds[1] = nw[1];
-        ds[2] = nw[2];
+        ds[0] = n0;
+        ds[1] = n1;
+        ds[2] = n2;
     }
     PatchSet nu, od;
-    decode_patches(p, nw[0], nf, k, nu);
+    decode_patches(p, n0, nf, k, nu);
     decode_patches(p, ocells, of, k, od);
     float *o = obs + ((int64_t)k * p.E + e) * HW;
 #pragma unroll
@@ -822,6 +825,11 @@ __global__ void __launch_bounds__(DELTA_T) obs_delta_kernel(Params p, float *__r
         for (int q2 = 0; q2 < NPATCH_MAX; ++q2) st = st && nu.c[q2] != c;
         if (st) o[c] = ((p.tb.roadbits[c >> 5] >> (c & 31)) & 1u) ? 0.0f : -1.0f;
     }
+}
+
+__global__ void __launch_bounds__(DELTA_T) obs_delta_kernel(Params p, float *__restrict__ obs,
+                                                            uint32_t *__restrict__ saved) {
+    obs_delta_block(p, obs, saved, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1451,6 +1459,22 @@ __global__ void __launch_bounds__(128) fear_rows_kernel(Params p, PatchArgs a, u
     gwrows::rows_block<N + 1, 16, 2, 2>(a, r % nrx, (int)(r / nrx), reinterpret_cast<float4 (*)[64 * 4]>(dynr));
 }
 
+// fear_v2's wide blocks and the delta obs writer in ONE launch (the step's writer "rides"): both
+// read only what the world update wrote, so a steady step is two launches on the caller's stream,
+// with no obs stream, no event and no cross-queue wait between them.  FeAR blocks first: theirs is
+// the long chain; the writer's blocks fill the CU slots they leave.  One launch has one footprint:
+// the writer's blocks also reserve the FeAR tables' dynamic LDS and fear_block's static state.
+static_assert(DELTA_T == GW_FEAR_T, "fear_delta_kernel: both block roles on one block size");
+template <int N, int KMAX>
+__global__ void __launch_bounds__(GW_FEAR_T) fear_delta_kernel(Params p, float *__restrict__ obs,
+                                                               uint32_t *__restrict__ saved, uint32_t nfear) {
+    if (blockIdx.x < nfear) {
+        fear_block<N, KMAX, true, GW_FEAR_T>(p, blockIdx.x);
+        return;
+    }
+    obs_delta_block(p, obs, saved, blockIdx.x - nfear);
+}
+
 // ---------------------------------------------------------------------------------------
 // fear_alt_kernel (gw_set_fear_alt): the per-action counterfactual FeAR table of a step,
 //   fear_alt[e][k][a] = np.sum(Resp) of FeAR_4_one_actor(actor = k) with k playing a,
@@ -1814,6 +1838,10 @@ struct Env {
     hipStream_t dest_stream[gwdest::SLOTS] = {nullptr};
     bool dest_written[gwdest::SLOTS] = {false};
     int64_t n_obs_full = 0, n_obs_delta = 0;  // gw_step obs writes by the full / the delta writer
+    // the delta writer of an eager async step as a block role of the FeAR launch on the caller's
+    // stream (fear_delta_kernel; ride_slot has the conditions).  gw_set_obs_ride(env, 0): never
+    bool obs_ride = true;
+    int64_t n_obs_ride = 0;  // steps whose writer rode (counted in n_obs_delta too)
     // tables
     uint8_t *okmask = nullptr, *policy = nullptr, *mdr = nullptr;
     double *cdf = nullptr, *resp = nullptr;
@@ -2123,7 +2151,10 @@ hipError_t launch_step(const Env *env, const gw::Params &p, hipStream_t s) {
 // fear_v2 after a deferred world update; with `a`: fear_rows_kernel, the same FeAR blocks plus the
 // windows' row writer (a's P x P windows, whole env range) as the two block roles of one launch.
 // Their stats rows follow the world-update kernel's.
-hipError_t launch_fear(const Env *env, const gw::Params &p0, hipStream_t s, const gw::PatchArgs *a = nullptr) {
+// With `obs`: fear_delta_kernel, the wide FeAR blocks plus the delta obs writer of the whole env
+// range into `obs`, whose saved descriptors are `saved`.
+hipError_t launch_fear(const Env *env, const gw::Params &p0, hipStream_t s, const gw::PatchArgs *a = nullptr,
+                       float *obs = nullptr, uint32_t *saved = nullptr) {
     gw::Params p = p0;
     const size_t dyn = fear_lds(p);
     const int64_t count = p.e_end - p.e_begin;
@@ -2139,6 +2170,14 @@ hipError_t launch_fear(const Env *env, const gw::Params &p0, hipStream_t s, cons
             // one footprint for both roles: the FeAR tables or the row writer's 2 x 64 x 4 float4 slices
             gw_launch((gw::fear_rows_kernel<N, KMAX, WIDE>), dim3(nfear + nrx * (unsigned)a->K), dim3(128),
                       std::max(dyn, sizeof(float4) * 2 * 64 * 4), s, p, *a, nfear, nrx);
+        } else if (obs) {
+            if constexpr (WIDE) {
+                const unsigned ndelta = (unsigned)ceil_div(count, gw::DELTA_T / env->K);
+                gw_launch((gw::fear_delta_kernel<N, KMAX>), dim3(nfear + ndelta), dim3(GW_FEAR_T), dyn, s, p, obs,
+                          saved, nfear);
+            } else {
+                return hipErrorInvalidValue;  // ride_slot: wide FeAR blocks only
+            }
         } else {
             gw_launch((gw::fear_v2<N, KMAX, WIDE>), dim3(nfear), dim3(WIDE ? GW_FEAR_T : 128), dyn,
                       s, p);
@@ -2513,8 +2552,26 @@ gw_status step_fear_full(Env *env, const gw::Params &p, hipStream_t s) {
 // ran inside the step kernel: nothing to launch), then the fear_alt table, FeAL and the full matrix.  A step without obs
 // outputs whose armed window request (gw_step_patch_next) meets the row writer's conditions over
 // the whole env range writes the windows in the same launch (fear_rows_kernel).
-gw_status fear_stage(Env *env, const gw::Params &p, hipStream_t s) {
-    if (defer_fear(env)) {
+// ride >= 0 (ride_slot): the step's delta obs writer into that destination slot is a block role of
+// the FeAR launch (fear_delta_kernel), so the obs are ordered on s like FeAR's own outputs.
+gw_status fear_stage(Env *env, const gw::Params &p, hipStream_t s, int ride = -1) {
+    if (ride >= 0) {
+        // launch_obs_dest's order and bookkeeping for a delta write: after the slot's last writer
+        // where that ran on another stream; the slot's event rides in the launch as its stop event,
+        // for the next writer that runs on another stream
+        if (env->dest_written[ride] && env->dest_stream[ride] != s)
+            HIP_TRY(hipStreamWaitEvent(s, env->dest_ev[ride], 0));
+        {
+            SpanGuard span(env, env->profiling, GW_SPAN_FEAR);
+            GW_TRY(span.status);
+            BindStop bind(env->dest_ev[ride]);
+            HIP_TRY(launch_fear(env, p, s, nullptr, p.out.obs, env->dest_desc[ride]));
+        }
+        env->n_obs_delta++;
+        env->n_obs_ride++;
+        env->dest_stream[ride] = s;
+        env->dest_written[ride] = true;
+    } else if (defer_fear(env)) {
         Env::PatchReq &rq = env->patch_req;
         const int P = rq.P;
         const bool rows = !p.out.obs && !p.out.final_obs && rq.armed && rq.patch && P >= 2 && P <= 16 &&
@@ -2572,6 +2629,29 @@ gw_status step_merged_async(Env *env, gw::Params &p, hipStream_t s) {
 // overlaps FeAR and the world update + FeAR of step t+1, which read only the state.
 // The descriptor is double-buffered: step t writes desc_buf[nb]; obs_kernel(t-2) read
 // that buffer, so the world update waits for it.
+//
+// The ride: an eager step whose writer is the delta writer of the whole env range needs no obs
+// stream.  The writer reads only the descriptors the world update wrote, as FeAR does, so it runs
+// as a block role of the FeAR launch (fear_delta_kernel) and the step is two plain launches on s:
+// no world_ev, no obs_done, no cross-queue wait.  The descriptor buffers still alternate, so a
+// step that does not ride (a first write into a destination, profiling, a capture, ...) pipelines
+// as before; a writer of such a step still in flight on an obs stream is waited for once.
+
+// the destination slot of p.out.obs if this step's writer rides in the FeAR launch on s, else -1
+gw_status ride_slot(Env *env, const gw::Params &p, hipStream_t s, int *slot) {
+    *slot = -1;
+    if (!env->obs_ride || !defer_fear(env) || !env->fear_wide || env->obs_lazy || env->fear_async ||
+        env->obs_queued || env->obs_chunks != 1 || env->profiling || !env->obs_delta || env->obs_bf16 || !p.out.obs ||
+        p.out.final_obs || p.rmask || p.e_begin != 0 || p.e_end != env->E)
+        return GW_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone) return GW_OK;  // launch_obs_dest forgets the destinations
+    const int i = env->dests.find(p.out.obs, GW_OBS_F32);
+    if (i >= 0 && env->dest_desc[i]) *slot = i;
+    return GW_OK;
+}
+
 gw_status step_defer_async(Env *env, gw::Params &p, hipStream_t s) {
     GW_TRY(ensure_obs_stream(env));
     // the world update + FeAR chain runs on the caller's stream itself (no fork / join hops
@@ -2583,6 +2663,19 @@ gw_status step_defer_async(Env *env, gw::Params &p, hipStream_t s) {
     GW_TRY(flush_obs(env, env->sync_ev[0]));       // lazy: obs_kernel(t-1), behind that work
     const int nb = env->dcur ^ 1;
     p.desc = env->desc_buf[nb];
+    int ride = -1;
+    GW_TRY(ride_slot(env, p, s, &ride));
+    if (ride >= 0) {
+        if (env->obs_pending[nb]) {  // a writer of an earlier step that did not ride read this buffer
+            HIP_TRY(hipStreamWaitEvent(s, env->obs_done[nb], 0));
+            env->obs_pending[nb] = false;  // s is behind it from here on
+        }
+        GW_TRY(world_update(env, p, s));
+        GW_TRY(fear_stage(env, p, s, ride));
+        env->dcur = nb;
+        env->desc = env->desc_buf[nb];
+        return GW_OK;
+    }
     if (on_aux) HIP_TRY(hipStreamWaitEvent(ws, env->sync_ev[0], 0));
     if (env->obs_pending[nb]) HIP_TRY(hipStreamWaitEvent(ws, env->obs_done[nb], 0));
     GW_TRY(world_update(env, p, ws, env->world_ev));
@@ -3268,6 +3361,23 @@ gw_status gw_obs_delta_counts(void *handle, int64_t out[2]) {
     if (!env || !out) return fail(GW_ERR_ARG, "null argument");
     out[0] = env->n_obs_full;
     out[1] = env->n_obs_delta;
+    return GW_OK;
+}
+
+gw_status gw_set_obs_ride(void *handle, int on) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "null env");
+    if (on != 0 && on != 1) return fail(GW_ERR_ARG, "gw_set_obs_ride: 0 or 1");
+    // between any two steps: the destinations' events and streams and the descriptor buffers'
+    // pending writers order a riding step and a pipelined one either way round
+    env->obs_ride = on != 0;
+    return GW_OK;
+}
+
+gw_status gw_obs_ride_count(void *handle, int64_t *out) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env || !out) return fail(GW_ERR_ARG, "null argument");
+    *out = env->n_obs_ride;
     return GW_OK;
 }
 

@@ -196,7 +196,7 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_maddpg_desc_workspace_floats", "gw_maddpg_desc_prime", "gw_maddpg_desc_update", "gw_count_sims",
            "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
            "gw_set_fear_alt", "gw_fear_regret_accum",
-           "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts",
+           "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts", "gw_set_obs_ride", "gw_obs_ride_count",
            "gw_set_feal", "gw_feal_accum", "gw_set_fear_full", "gw_fear_preview", "gw_fear_shield",
            "gw_fear_shield_joint"]
 
@@ -425,6 +425,10 @@ def _declare(L):
     L.gw_obs_dest_forget.restype = C.c_int
     L.gw_obs_delta_counts.argtypes = [p, C.POINTER(C.c_int64)]
     L.gw_obs_delta_counts.restype = C.c_int
+    L.gw_set_obs_ride.argtypes = [p, C.c_int]
+    L.gw_set_obs_ride.restype = C.c_int
+    L.gw_obs_ride_count.argtypes = [p, C.POINTER(C.c_int64)]
+    L.gw_obs_ride_count.restype = C.c_int
     L.gw_set_fear_blocks.argtypes = [p, C.c_int]
     L.gw_set_fear_blocks.restype = C.c_int
     L.gw_destroy.argtypes = [p]

@@ -220,6 +220,16 @@ class VecGridEnv:
         self.obs_delta = False
         if obs and obs_dtype == torch.float32 and os.environ.get("GW_OBS_DELTA", "1") != "0":
             self.set_obs_delta(True)
+        # GW_OBS_RIDE=0: the delta writer of an eager async step never runs inside the FeAR launch
+        # (gw_set_obs_ride; A/B, the results are the same).  Only 0 or 1: the library refuses the rest
+        ride = os.environ.get("GW_OBS_RIDE")
+        if ride is not None:
+            try:
+                _lib.check(self.lib.gw_set_obs_ride(self.handle, int(ride) if ride in ("0", "1") else -1),
+                           "gw_set_obs_ride (GW_OBS_RIDE)")
+            except _lib.GwError:
+                self.close()
+                raise
         self.obs_async = False
         self.fear_async = False
         # the kernel path gw_create picked (GW_KERNEL, or by batch size: gw_kernel_path)
@@ -361,6 +371,12 @@ class VecGridEnv:
         out = (C.c_int64 * 2)()
         _lib.check(self.lib.gw_obs_delta_counts(self.handle, out), "gw_obs_delta_counts")
         return int(out[0]), int(out[1])
+
+    def obs_ride_count(self) -> int:
+        """Steps whose delta obs writer ran inside the FeAR launch on the step's stream (gw_obs_ride_count)."""
+        out = C.c_int64(0)
+        _lib.check(self.lib.gw_obs_ride_count(self.handle, C.byref(out)), "gw_obs_ride_count")
+        return int(out.value)
 
     def _build_into(self, over: dict):
         """(GwStepOut, result fields, StepResult) for the destination buffers ``over``."""
