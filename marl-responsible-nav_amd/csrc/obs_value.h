@@ -1,6 +1,6 @@
 // obs_value.h — internal: the observation encoding's one agent-cell rule, shared by the obs writer
 // (gridenv.hip), the window writers (patch_ops.hip, window_rows.h), the fused actors (actor_ops.hip)
-// and the descriptor learner's samplers (rollout_ops.hip, maddpg_ops.hip).
+// and the descriptor learner's samplers (rollout_ops.hip, maddpg_desc.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // philox.h — internal: Philox4x32-10, the library's one generator (counter-based, graph- and
 // shard-invariant keyed draws): the env's draws (gridenv.hip: keyed by global env id, episode, step,
 // tag), the actors' Gumbel noise (actor_ops.hip) and the learner's sampling and Gumbel noise
-// (rollout_ops.hip, maddpg_ops.hip).
+// (rollout_ops.hip, maddpg_dense.hip, maddpg_desc.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

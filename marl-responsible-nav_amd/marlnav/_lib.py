@@ -25,7 +25,8 @@ MEASURE = os.environ.get("MARLNAV_MEASURE", "0") == "1"
 LIB_PATH = os.path.join(CSRC, "libgridenv_measure.so" if MEASURE else "libgridenv.so")
 HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_ops.hip"),
                os.path.join(CSRC, "actor_ops.hip"), os.path.join(CSRC, "rollout_ops.hip"),
-               os.path.join(CSRC, "maddpg_ops.hip"), os.path.join(CSRC, "patch_ops.hip"),
+               os.path.join(CSRC, "maddpg_dense.hip"), os.path.join(CSRC, "maddpg_desc.hip"),
+               os.path.join(CSRC, "patch_ops.hip"),
                os.path.join(CSRC, "fear_full.hip"), os.path.join(CSRC, "fear_preview.hip"),
                os.path.join(CSRC, "fear_shield_joint.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
@@ -36,7 +37,8 @@ SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.jo
                                    os.path.join(CSRC, "obs_value.h"), os.path.join(CSRC, "obs_dest.h"),
                                    os.path.join(CSRC, "resp_tables.h"), os.path.join(CSRC, "cf_env.h"),
                                    os.path.join(CSRC, "draw_action.h"), os.path.join(CSRC, "fear_shield.h"),
-                                   os.path.join(CSRC, "np_sum.h")]
+                                   os.path.join(CSRC, "np_sum.h"), os.path.join(CSRC, "mlp_rows.h"),
+                                   os.path.join(CSRC, "grad_core.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

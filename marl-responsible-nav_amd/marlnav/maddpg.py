@@ -222,7 +222,7 @@ class MADDPG:
             m.requires_grad_(False)
         self._graph = None
         self._graphs = None  # world > 1: three graph segments between the gradient all-reduces
-        # the fused update (csrc/maddpg_ops.hip: two launch sequences carry the two backward
+        # the fused update (csrc/maddpg_dense.hip: two launch sequences carry the two backward
         # passes; GW_FUSED_LEARN=0 selects the torch-autograd composition)
         import os
         self.fused = (self.flat and os.environ.get("GW_FUSED_LEARN", "1") != "0"
@@ -314,7 +314,7 @@ class MADDPG:
         self._desc_stale = True  # weights changed outside the descriptor learner
         return self._learn_finish(ctx)
 
-    # ---- the descriptor learner (csrc/maddpg_ops.hip gw_maddpg_desc_update) -------------------
+    # ---- the descriptor learner (csrc/maddpg_desc.hip gw_maddpg_desc_update) -------------------
     def desc_capable(self, replay, generator=None) -> bool:
         """Whether an update on ``replay`` can run as the descriptor learner: one rank, the fused
         flat networks with in-kernel draws, a ReplayRing currently serving descriptor rows, a batch

@@ -1,4 +1,4 @@
-"""The dense fused MADDPG update (csrc/maddpg_ops.hip: gw_maddpg_critic_grads / gw_maddpg_actor_grads)
+"""The dense fused MADDPG update (csrc/maddpg_dense.hip: gw_maddpg_critic_grads / gw_maddpg_actor_grads)
 against a float64 restatement of the update (tests/_maddpg_ref64.py, tied to the per-agent loop in
 tests/test_maddpg_ref64_cpu.py) at the shapes where the kernels branch (tests/_learner_cases.py):
 D % 4, D % 16, D / K*D / K*D + 9K modulo the 64-input chunks, more than RED_PRE chunks, row tiles

@@ -1,4 +1,4 @@
-"""The fused MADDPG update (csrc/maddpg_ops.hip: gw_maddpg_critic_grads / gw_maddpg_actor_grads,
+"""The fused MADDPG update (csrc/maddpg_dense.hip: gw_maddpg_critic_grads / gw_maddpg_actor_grads,
 the default GPU learner) against the torch-autograd composition of the same update
 (marlnav/maddpg.py with GW_FUSED_LEARN=0, itself pinned to the per-agent agilerl-style loop in
 tests/test_maddpg.py) and against that per-agent loop.

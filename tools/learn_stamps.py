@@ -1,4 +1,4 @@
-"""Summarise GW_LEARN_STAMP block stamps of the descriptor learner (maddpg_ops.hip DSTAMP).
+"""Summarise GW_LEARN_STAMP block stamps of the descriptor learner (maddpg_desc.hip DSTAMP).
 
 usage: python tools/learn_stamps.py <stamp file> [skip updates]
 Per launch (critic tail, critic grads, actor tail, actor grads): the median over updates of the
