@@ -107,6 +107,32 @@ gw_status gw_replay_gather_desc(const gw_obs_source *src, const uint32_t *desc, 
                                 int64_t *tr_out, float *x_out, float *xn_out, uint64_t seed, const int32_t *ctr,
                                 void *stream);
 
+/* gw_replay_gather_desc for a local-window rollout whose ring holds descriptors ONLY
+ * (marlnav/rollout.py ReplayRing(patch=P, desc="only")): the obs rows are each agent's P x P window
+ * (gw_obs_patch, include/gridenv.h) expanded straight from the descriptors, so the rollout step runs no
+ * window writer and the ring keeps 48 bytes per env and slot instead of 2 * K * P * P * 4.  The argument
+ * list and the sampling rule (n, step, tr, nx, explicit u / env or the in-kernel Philox draws with the
+ * 'SAMP' tag) and probs_out, reward_out, term_out, tr_out are gw_replay_gather_desc's; with HW := P * P
+ *   state[k, b]      = agent k's window of the obs of descriptor slot tr;
+ *   next_state[k, b] = the window of descriptor slot nx, from its terminal half (words 8-11, apple bits
+ *                      16-23) when done[tr, e] is set, as gw_replay_gather_desc chooses;
+ *   x_out[b] = [state[0, b] .. state[K-1, b], probs_out[0, b] .. probs_out[K-1, b]] (K * P * P + 9 K floats);
+ *   xn_out[b][0, K * P * P) = the next windows (its action slots are left to the caller);
+ * state / next_state may be NULL when x_out and xn_out are given.
+ * The window: rows and columns -P/2 .. P-1-P/2 around agent k's own cell IN THAT HALF OF THAT DESCRIPTOR
+ * (the spawn cell of a reset-encoded obs, the terminal cell of the terminal half), cells outside the grid
+ * -1, the map value else, then the descriptor's patched cells (the apple first, then agents 0 .. N-1, a
+ * later one overrides): bit for bit gw_obs_patch(env, P, patch, final_patch) of the step that filled the
+ * slot.  1 <= P <= 129 (gw_obs_patch's range), src->H * src->W <= 4096, desc 16-byte aligned; anything
+ * else returns GW_ERR_ARG with a gw_last_error message.  One launch, one 256-thread block per (b, k); no
+ * atomics; e, the descriptor cells and the apple cells are clamped before they index anything. */
+gw_status gw_replay_gather_desc_patch(const gw_obs_source *src, const uint32_t *desc, const float *probs,
+                                      const double *reward, const uint8_t *term, const uint8_t *done,
+                                      const int64_t *t_dev, const float *u, const int64_t *env, int64_t S,
+                                      int64_t B, int32_t P, float *state, float *next_state, float *probs_out,
+                                      double *reward_out, uint8_t *term_out, int64_t *tr_out, float *x_out,
+                                      float *xn_out, uint64_t seed, const int32_t *ctr, void *stream);
+
 /* One evaluation step's totals (customeval.py:70-133 over E episodes at once; marlnav/evaluate.py):
  * for every env e with active[e]:  counts[0] += crashes[e];  counts[1] += apples[e];
  * counts[2] += 1;  *fear_total += sum_k fear[e, k];  then active[e] = 0 if done[e].

@@ -32,6 +32,10 @@ def main(argv=None):
     ap.add_argument("--updates-per-step", type=int, default=None,
                     help="MADDPG updates per env step (default: the reference rule, E // LEARN_STEP)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--patch", type=int, default=0,
+                    help="P > 0: train the local-window policies on each agent's egocentric P x P window (an opt-in "
+                         "input format; the reference observes the whole grid).  With the MLP head the replay ring "
+                         "holds obs descriptors only and the step runs no window writer")
     ap.add_argument("--save", default=None)
     args = ap.parse_args(argv)
     with open(args.config) as f:
@@ -49,12 +53,14 @@ def main(argv=None):
     torch.cuda.manual_seed(hp["SEED"] + rank)  # each rank samples its own replay batches
     offset, count = shard(args.envs, rank, world)
     env = VecGridEnv(args.scenario, num_envs=count, fear=hp["WITH_FEAR"], fear_weight=hp["FeAR_weight"],
-                     max_steps=hp["TRAIN_STEPS"], seed=hp["SEED"], env_offset=offset, stats=True, final_obs=True)
-    m = MADDPG(env.K, env.H, env.W, arch=hp["ARCH"], lr_actor=hp["LR_ACTOR"], lr_critic=hp["LR_CRITIC"],
-               gamma=hp["GAMMA"], tau=hp["TAU"], batch_size=hp["BATCH_SIZE"], learn_step=hp["LEARN_STEP"],
+                     max_steps=hp["TRAIN_STEPS"], seed=hp["SEED"], env_offset=offset, stats=True,
+                     final_obs=not args.patch, obs=not args.patch)
+    m = MADDPG(env.K, args.patch or env.H, args.patch or env.W, arch=hp["ARCH"], lr_actor=hp["LR_ACTOR"],
+               lr_critic=hp["LR_CRITIC"], gamma=hp["GAMMA"], tau=hp["TAU"], batch_size=hp["BATCH_SIZE"], learn_step=hp["LEARN_STEP"],
                device=env.device, seed=hp["SEED"], capturable=not args.no_graph)
     tr = MADDPGTrainer(env, m, memory_size=hp["MEMORY_SIZE"], updates_per_step=args.updates_per_step,
-                       graph=False if args.no_graph else "launches", seed=hp["SEED"])
+                       graph=False if args.no_graph else "launches", seed=hp["SEED"],
+                       patch=args.patch)
     tr.reset()
     for it in range(args.iters):
         s = tr.train(hp["TRAIN_STEPS"])  # the statistics are all-reduced over the ranks

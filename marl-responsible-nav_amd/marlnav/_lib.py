@@ -26,7 +26,7 @@ LIB_PATH = os.path.join(CSRC, "libgridenv_measure.so" if MEASURE else "libgriden
 HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_ops.hip"),
                os.path.join(CSRC, "actor_ops.hip"), os.path.join(CSRC, "rollout_ops.hip"),
                os.path.join(CSRC, "maddpg_dense.hip"), os.path.join(CSRC, "maddpg_desc.hip"),
-               os.path.join(CSRC, "patch_ops.hip"),
+               os.path.join(CSRC, "patch_ops.hip"), os.path.join(CSRC, "replay_patch.hip"),
                os.path.join(CSRC, "fear_full.hip"), os.path.join(CSRC, "fear_preview.hip"),
                os.path.join(CSRC, "fear_shield_joint.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
@@ -38,7 +38,7 @@ SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.jo
                                    os.path.join(CSRC, "resp_tables.h"), os.path.join(CSRC, "cf_env.h"),
                                    os.path.join(CSRC, "draw_action.h"), os.path.join(CSRC, "fear_shield.h"),
                                    os.path.join(CSRC, "np_sum.h"), os.path.join(CSRC, "mlp_rows.h"),
-                                   os.path.join(CSRC, "grad_core.h")]
+                                   os.path.join(CSRC, "grad_core.h"), os.path.join(CSRC, "desc_rows.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -195,6 +195,7 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_pipeline_state_bytes", "gw_pipeline_save", "gw_pipeline_load",
            "gw_gather_pack_scratch", "gw_gather_pack", "gw_gather_unpack_plan_cap", "gw_gather_unpack",
            "gw_adam_soft_step", "gw_obs_desc_copy", "gw_replay_gather_desc",
+           "gw_replay_gather_desc_patch",
            "gw_maddpg_desc_workspace_floats", "gw_maddpg_desc_prime", "gw_maddpg_desc_update", "gw_count_sims",
            "gw_actor_images_view", "gw_maddpg_desc_update_img", "gw_fear_row_accum",
            "gw_set_fear_alt", "gw_fear_regret_accum",
@@ -374,6 +375,9 @@ def _declare(L):
     L.gw_replay_gather_desc.argtypes = [C.POINTER(GwObsSource)] + [p] * 8 + [C.c_int64, C.c_int64] + [p] * 8 + \
         [C.c_uint64, p, p]
     L.gw_replay_gather_desc.restype = C.c_int
+    L.gw_replay_gather_desc_patch.argtypes = [C.POINTER(GwObsSource)] + [p] * 8 + [C.c_int64, C.c_int64, C.c_int32] + \
+        [p] * 8 + [C.c_uint64, p, p]
+    L.gw_replay_gather_desc_patch.restype = C.c_int
     L.gw_count_sims.argtypes = [p, p]
     L.gw_count_sims.restype = C.c_int
     L.gw_obs_desc_copy.argtypes = [p, p, p]

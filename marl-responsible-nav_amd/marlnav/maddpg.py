@@ -318,8 +318,13 @@ class MADDPG:
     def desc_capable(self, replay, generator=None) -> bool:
         """Whether an update on ``replay`` can run as the descriptor learner: one rank, the fused
         flat networks with in-kernel draws, a ReplayRing currently serving descriptor rows, a batch
-        of 16..256 rows in 16-row tiles (GW_DESC_LEARN=0: never)."""
+        of 16..256 rows in 16-row tiles (GW_DESC_LEARN=0: never).  Never a window ring
+        (``ReplayRing(patch=P, desc="only")``): its descriptors expand to P x P windows, which the
+        full-grid descriptor learner does not compute; its updates are the dense fused learner on the
+        rows of gw_replay_gather_desc_patch."""
         import os
+        if getattr(replay, "patch", 0) or getattr(replay, "obs", None) is None:
+            return False
         return (generator is None and self.device.type == "cuda" and self.world <= 1 and self._draws_in_kernel()
                 and getattr(replay, "use_desc", False) and 16 <= self.batch_size <= 256
                 and self.batch_size % 16 == 0 and self.K <= _lib.GW_MAX_AGENTS and replay.K == self.K

@@ -34,20 +34,35 @@ from .vec_env import VecGridEnv
 class ReplayRing:
     """S steps of E transitions each, in HBM.  obs slots are written by the env directly."""
 
-    def __init__(self, env: VecGridEnv, slots: int, patch: int = 0, desc: bool = False):
+    def __init__(self, env: VecGridEnv, slots: int, patch: int = 0, desc: bool | str = False):
         """patch > 0: the ring holds the agents' egocentric patch x patch observations
         (VecGridEnv.obs_patch) instead of the full grids.
-        desc (full-grid obs on the GPU): also keep each step's 48-byte obs descriptors per slot
-        ([S][E][12] u32, 3 MB per slot at 65,536 envs); ``sample`` then expands the sampled rows
-        from them (gw_replay_gather_desc, the same values bit for bit), so a learner that follows a
-        step never waits for that step's obs writer.  Rollout fills it (``Rollout(desc_ring=True)``)."""
+        desc=True (full-grid obs on the GPU; ignored with patch): also keep each step's 48-byte obs
+        descriptors per slot ([S][E][12] u32, 3 MB per slot at 65,536 envs); ``sample`` then expands the
+        sampled rows from them (gw_replay_gather_desc, the same values bit for bit), so a learner that
+        follows a step never waits for that step's obs writer.  Rollout fills it (``Rollout(desc_ring=True)``).
+        desc="only" (with patch > 0, on the GPU, H * W <= 4096): the ring holds the descriptors and NO
+        windows (``obs`` and ``final_obs`` are None: 48 bytes per env and slot instead of 2 K P^2 4);
+        ``sample`` expands the sampled P x P windows from them (gw_replay_gather_desc_patch: bit for bit
+        what gw_obs_patch would have written), so the rollout step needs no window writer.  Rollout fills
+        it (``Rollout(patch=P, desc_ring="only")``).  There is no CPU path: anything else raises."""
         self.S = max(2, int(slots))
         K, E, H, W, dev = env.K, env.E, env.H, env.W, env.device
+        self.patch = int(patch)
+        only = isinstance(desc, str)
+        if only and desc != "only":
+            raise ValueError('ReplayRing(desc=...): True, False or "only"')
+        if only and not (patch and dev.type == "cuda" and H * W <= 4096):
+            raise ValueError('ReplayRing(desc="only") needs patch > 0, a GPU env and H * W <= 4096 '
+                             "(the descriptor-only window ring has no CPU path)")
         if patch:
             H = W = int(patch)
+        self.row_shape = (H, W)  # of one agent's obs row as ``sample`` returns it
         od = env.obs_dtype if not patch else torch.float32  # bf16 obs (lossless) halves the ring
-        self.obs = torch.zeros((self.S, K, E, H, W), dtype=od, device=dev)
-        self.final_obs = torch.zeros((self.S, K, E, H, W), dtype=od, device=dev)
+        self.obs = self.final_obs = None
+        if not only:
+            self.obs = torch.zeros((self.S, K, E, H, W), dtype=od, device=dev)
+            self.final_obs = torch.zeros((self.S, K, E, H, W), dtype=od, device=dev)
         self.probs = torch.zeros((self.S, K, E, 9), dtype=torch.float32, device=dev)
         self.reward = torch.zeros((self.S, E, K), dtype=torch.float64, device=dev)
         self.term = torch.zeros((self.S, E, K), dtype=torch.uint8, device=dev)
@@ -57,7 +72,8 @@ class ReplayRing:
         self.E, self.K = E, K
         self.desc = None
         self.desc_ok = False  # every descriptor slot matches its obs slot (set by Rollout.reset)
-        if desc and not patch and dev.type == "cuda" and H * W <= 4096:  # (the expansion's cell limit)
+        self.desc_only = only  # the window ring without windows: ``sample`` has the descriptors alone
+        if only or (desc and not patch and dev.type == "cuda" and H * W <= 4096):  # (the expansion's cell limit)
             self.desc = torch.zeros((self.S, E, 12), dtype=torch.int32, device=dev)
             self._src = _lib.GwObsSource()
             _lib.check(_lib.load().gw_obs_view(env.handle, C.byref(self._src)), "gw_obs_view")
@@ -71,20 +87,28 @@ class ReplayRing:
     def state_dict(self) -> dict:
         """The ring's contents and fill state (MADDPGAgent.save_checkpoint's memory.pkl,
         maddpg/agent.py:255-266; safetensors here, nothing is pickled)."""
-        out = {n: getattr(self, n) for n in self._TENSORS}
+        out = {n: getattr(self, n) for n in self._tensors()}
         out["t"] = torch.tensor([self.t], dtype=torch.int64)
         out["t_dev"] = self.t_dev.reshape(1)
         return out
 
+    def _tensors(self):
+        """What a checkpoint carries: the descriptor-only window ring's ``desc`` in place of the windows."""
+        return ("desc",) + self._TENSORS[2:] if self.desc_only else self._TENSORS
+
     @torch.no_grad()
     def load_state_dict(self, sd: dict):
-        for n in self._TENSORS:
+        if self.desc_only and "desc" not in sd:
+            raise ValueError("replay ring desc: missing (the checkpoint holds a dense window ring)")
+        for n in self._tensors():
             if tuple(sd[n].shape) != tuple(getattr(self, n).shape):
                 raise ValueError(f"replay ring {n}: shape {tuple(sd[n].shape)} != {tuple(getattr(self, n).shape)}")
             getattr(self, n).copy_(sd[n])
         self.t = int(sd["t"][0])
         self.t_dev.copy_(sd["t_dev"].reshape(()))
-        self.desc_ok = False  # the descriptors are not saved: dense rows until the next reset
+        # full-grid ring: the descriptors are not saved: dense rows until the next reset.  The
+        # descriptor-only ring has just loaded them: its rows are the saved ring's
+        self.desc_ok = self.desc_only
 
     @torch.no_grad()
     def sample(self, batch: int, generator: torch.Generator | None = None, return_idx: bool = False,
@@ -96,7 +120,9 @@ class ReplayRing:
         build from them, from the same gather launch (x_next's action slots left to the learner)."""
         if self.t <= 0:
             raise RuntimeError("empty replay ring")
-        dev = self.obs.device
+        dev = self.probs.device
+        if self.desc_only and not self.use_desc:
+            raise RuntimeError("descriptor-only replay ring: no descriptors yet (Rollout.reset fills slot 0)")
         if dev.type == "cuda":
             return self._sample_hip(batch, generator, return_idx, critic_in, extra_uniform, self.use_desc, philox)
         n = torch.clamp(self.t_dev, min=1, max=self.S - 1)
@@ -126,7 +152,7 @@ class ReplayRing:
         has no RNG bookkeeping either); returns no extra uniforms and no env indices, and with
         critic_in on the descriptor ring the state / next_state tensors come back UNWRITTEN
         (only their shapes are meaningful: the fused learner reads the critic rows)."""
-        dev = self.obs.device
+        dev = self.probs.device
         if philox is not None:
             seed, ctr = int(philox[0]), philox[1]
             u = env = None
@@ -135,8 +161,8 @@ class ReplayRing:
             u_all = torch.rand((batch + int(extra),), device=dev, generator=generator)
             u = u_all[:batch]
             env = torch.randint(0, self.E, (batch,), device=dev, generator=generator)
-        K, HW = self.K, self.obs.shape[-2] * self.obs.shape[-1]
-        state = torch.empty((K, batch) + tuple(self.obs.shape[-2:]), device=dev, dtype=torch.float32)
+        K, HW = self.K, self.row_shape[0] * self.row_shape[1]
+        state = torch.empty((K, batch) + tuple(self.row_shape), device=dev, dtype=torch.float32)
         next_state = torch.empty_like(state)
         probs = torch.empty((K, batch, 9), device=dev, dtype=torch.float32)
         reward = torch.empty((batch, K), device=dev, dtype=torch.float64)
@@ -156,7 +182,12 @@ class ReplayRing:
                 xn.data_ptr() if critic_in else None, seed, ctr.data_ptr() if ctr is not None else None, stream)
         up = u.data_ptr() if u is not None else None
         ep = env.data_ptr() if env is not None else None
-        if use_desc:
+        if self.desc_only:  # the window ring without windows: the P x P rows straight from the descriptors
+            _lib.check(_lib.load().gw_replay_gather_desc_patch(
+                C.byref(self._src), self.desc.data_ptr(), self.probs.data_ptr(), self.reward.data_ptr(),
+                self.term.data_ptr(), self.done.data_ptr(), self.t_dev.data_ptr(), up, ep,
+                self.S, batch, self.patch, *outs), "gw_replay_gather_desc_patch")
+        elif use_desc:
             _lib.check(_lib.load().gw_replay_gather_desc(
                 C.byref(self._src), self.desc.data_ptr(), self.probs.data_ptr(), self.reward.data_ptr(),
                 self.term.data_ptr(), self.done.data_ptr(), self.t_dev.data_ptr(), up, ep,
@@ -179,7 +210,7 @@ class Rollout:
     def __init__(self, env: VecGridEnv, actors: MultiAgentActors | None = None, replay_slots: int = 0,
                  training: bool = True, group=None, seed: int = 0, fused: bool | None = None,
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
-                 patch_async: bool | None = None, desc_ring: bool = False, resp_matrix: bool = False,
+                 patch_async: bool | None = None, desc_ring: bool | str = False, resp_matrix: bool = False,
                  fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
                  shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
@@ -202,7 +233,16 @@ class Rollout:
         step's actor (``fence()`` orders the ring slots).
         desc_ring (full-grid obs, GPU): the ring also keeps every step's obs descriptors and the
         learner samples from them (``ReplayRing(desc=True)``; ``learn_fence()`` then skips the
-        obs-writer wait, so the writer of step t overlaps the updates that follow it).
+        obs-writer wait, so the writer of step t overlaps the updates that follow it).  With patch > 0
+        True is ignored (the dense window ring).
+        desc_ring="only" (patch > 0, a replay ring, the fused MLP window actor; anything else raises
+        ValueError saying which): the ring keeps the 48-byte descriptors and NO windows
+        (``ReplayRing(patch=P, desc="only")``), and the step launches no window writer at all (no
+        gw_step_patch_next, gw_obs_patch or gw_patch_cnn_write_list; ``patch_async`` is off): the fused
+        actor reads the descriptors, and ``ReplayRing.sample`` expands the sampled windows from them
+        (gw_replay_gather_desc_patch, bit for bit the writer's windows).  ``capture`` works; ``resume()``
+        keeps serving descriptor rows (the carried-over obs becomes its slot's terminal half).  The CNN
+        head keeps the dense window ring: its listing shares the window writer's launch.
         resp_matrix (an env built with ``fear_rows=True``): every step's per-pair responsibility rows
         (StepResult.fear_row) are summed over the envs into a running [K, N] total
         (gw_fear_row_accum, one launch per step, also inside ``capture`` graphs); ``totals()`` then
@@ -247,6 +287,23 @@ class Rollout:
         self.patch = int(patch)
         if self.patch and actors is not None and (actors.H, actors.W) != (self.patch, self.patch):
             raise ValueError("Rollout(patch=P) needs actors built for a P x P input")
+        # desc_ring="only": the window ring keeps the descriptors and no windows, and the step runs no window
+        # writer.  The fused MLP window actor reads the descriptors alone; the CNN head's listing
+        # (gw_patch_cnn_write_list) shares the writer's launch, so it keeps the dense window ring
+        self.desc_only = isinstance(desc_ring, str)
+        if self.desc_only:
+            if desc_ring != "only":
+                raise ValueError('Rollout(desc_ring=...): True, False or "only"')
+            if not self.patch:
+                raise ValueError('Rollout(desc_ring="only") needs patch > 0 (full-grid obs: desc_ring=True)')
+            if not replay_slots:
+                raise ValueError('Rollout(desc_ring="only") needs a replay ring (replay_slots > 0)')
+            if not self.fused:
+                raise ValueError('Rollout(desc_ring="only") needs the fused window actor (an unfused actor '
+                                 "reads the written windows)")
+            if getattr(actors, "arch", "") != "mlp":
+                raise ValueError('Rollout(desc_ring="only") needs the fused MLP window actor: the CNN head\'s '
+                                 "listing shares the window writer's launch and keeps the dense window ring")
         self.replay = ReplayRing(env, replay_slots, patch=self.patch, desc=desc_ring) if replay_slots else None
         self._patch = None  # the current obs' patches when there is no ring
         # patch windows into the ring on a side stream: the fused actor of the next step reads the
@@ -261,7 +318,7 @@ class Rollout:
             env_pa = os.environ.get("GW_PATCH_ASYNC")
             patch_async = env_pa is not None and env_pa != "0"
         self.patch_async = (bool(patch_async) and bool(self.patch) and self.fused and self.replay is not None
-                            and env.device.type == "cuda")
+                            and env.device.type == "cuda" and not self.desc_only)  # (no writer to put aside)
         if self.patch_async:
             self._pstream = torch.cuda.Stream(device=env.device)
             self._pev = torch.cuda.Event()
@@ -440,7 +497,10 @@ class Rollout:
         self._lists_ready = False  # new descriptors: the next act lists itself
         if self.replay is not None:
             obs, mask = self.env.reset()
-            if self.patch:
+            if self.desc_only:  # the reset descriptors are the ring's first obs: no window is written
+                self._desc_copy(0)
+                self.replay.desc_ok = True
+            elif self.patch:
                 self.env.obs_patch(self.patch, out=self.replay.obs[0])
             else:
                 self.replay.obs[0].copy_(obs)
@@ -471,6 +531,29 @@ class Rollout:
         self._lists_ready = False
         t, S = rp.t, rp.S
         cur, prev = t % S, (t - 1) % S
+        if self.desc_only:
+            # no dense rows to fall back to: the carried-over obs (descriptor slot cur, the next state of the
+            # last stored transition) becomes the TERMINAL half of the slot the new episodes' reset
+            # descriptors go to, which is where sampling reads the next state of a done transition.  Where
+            # done[prev] was 0 that obs is a step encoding (a reset-encoded slot implies done[prev] == 1):
+            # its cells (words 0-3) go to words 8-11 and its apple bits 8-15 to bits 16-23 of word 4; where
+            # done[prev] was 1 the slot's own terminal half is kept
+            old = rp.desc[cur].clone()
+            self.env.reset()
+            self._desc_copy(cur)
+            if t > 0:
+                d = rp.desc[cur]
+                was_done = rp.done[prev].bool()
+                d[:, 8:12] = torch.where(was_done[:, None], old[:, 8:12], old[:, 0:4])
+                ap = torch.where(was_done, (old[:, 4] >> 16) & 0xFF, (old[:, 4] >> 8) & 0xFF)
+                d[:, 4] = (d[:, 4] & ~(0xFF << 16)) | (ap << 16)
+                rp.done[prev].fill_(1)
+            rp.desc_ok = True
+            self.t = t
+            self._calls = int(calls) if calls is not None else max(self._calls, t)
+            self._noise_base = self._calls - t
+            self._graphs = None
+            return
         if t > 0:
             rp.final_obs[prev].copy_(rp.obs[cur])
             rp.done[prev].fill_(1)
@@ -530,6 +613,8 @@ class Rollout:
                 into.update(obs=rp.obs[nxt], final_obs=rp.final_obs[cur])
                 if rp.desc is not None:  # the step kernels write the descriptors of slot nxt too
                     into["desc_copy"] = rp.desc[nxt]
+            elif self.desc_only:  # the descriptors of slot nxt are all the ring keeps of this step's obs
+                into["desc_copy"] = rp.desc[nxt]
             if self.gather is not None:
                 g = self.gather.into()
                 into["ep_return"] = g["ep_return"]
@@ -538,7 +623,8 @@ class Rollout:
             self._patch_join()  # the previous window writer has read the descriptors
             # the step's windows inside its FeAR launch (gw_step_patch_next; FeAR on and joined):
             # the MLP head's rollout, where no listing shares the writer's launch
-            step_patch = (self.patch and not self.patch_async and not self._cnn_list and env.fear_enabled and
+            step_patch = (self.patch and not self.desc_only and not self.patch_async and not self._cnn_list and
+                          env.fear_enabled and
                           not env.fear_async and env.device.type == "cuda" and
                           os.environ.get("GW_FEAR_PATCH", "1") != "0")
             if step_patch:
@@ -556,8 +642,8 @@ class Rollout:
                     env.obs_patch(self.patch, final=True, out=rp.obs[nxt], final_out=rp.final_obs[cur])
                 self._pev.record(self._pstream)
                 self._pev_live = True
-            elif self.patch and step_patch:
-                pass  # written by the step (gw_step_patch_next)
+            elif self.patch and (step_patch or self.desc_only):
+                pass  # written by the step (gw_step_patch_next), or not at all (the descriptor-only ring)
             elif self.patch:  # the step's obs / terminal obs as patches, straight into the ring
                 if not (self._cnn_list and not env.fear_async and not self._no_list and
                         self.actors.patch_cnn_write_list(env, self.patch, rp.obs[nxt], rp.final_obs[cur])):

@@ -56,8 +56,19 @@ def learn_schedule(idx_step: int, ring_t: int, ring_slots: int, global_envs: int
 
 class MADDPGTrainer:
     def __init__(self, env: VecGridEnv, maddpg: MADDPG, memory_size: int = 200_000, learning_delay: int = 0,
-                 updates_per_step: int | None = None, graph: bool | str = "launches", seed: int = 0):
+                 updates_per_step: int | None = None, graph: bool | str = "launches", seed: int = 0,
+                 patch: int = 0):
+        """patch = P > 0: train the local-window policies (X1): ``maddpg`` built for (H, W) = (P, P), the
+        rollout ``Rollout(patch=P)``.  Where the fused MLP window actor applies (``actors.fusable(env, P)``
+        with the MLP head, on the GPU) the replay ring is descriptor-only (``desc_ring="only"``: 48 bytes per
+        env and slot, no window writer in the step, the sampled windows expanded by
+        gw_replay_gather_desc_patch); else the dense window ring.  The update is the dense fused learner
+        with D = P * P either way, and checkpoints carry the ring's ``desc`` in place of its windows."""
         self.env, self.m = env, maddpg
+        self.patch = int(patch)
+        if self.patch and (maddpg.H, maddpg.W) != (self.patch, self.patch):
+            raise ValueError(f"MADDPGTrainer(patch={self.patch}) needs MADDPG(K, {self.patch}, {self.patch}), "
+                             f"got ({maddpg.H}, {maddpg.W})")
         # data parallelism: every decision that gates a learn() (and so its two gradient
         # all-reduces) is taken from GLOBAL quantities that every rank computes alike -- the global
         # env count, the smallest shard and the ring's step count (each rank steps once per step) --
@@ -72,10 +83,18 @@ class MADDPGTrainer:
         # the dense obs), launched behind it ("lazy"); the ring is fenced before every learn
         # the learner samples the ring's rows from its obs descriptors when the actor is fused
         # (Rollout(desc_ring)): an update never waits for the obs writer of the step before it
-        fusable = maddpg.actors.fusable(env)
-        self.rollout = Rollout(env, maddpg.actors, replay_slots=slots, training=True, seed=seed,
-                               obs_async="lazy" if fusable else False,
-                               desc_ring=fusable and env.device.type == "cuda")
+        if self.patch:
+            # window rollouts pipeline no dense obs; the fused MLP window actor reads the descriptors alone,
+            # so the ring keeps nothing else (the CNN head and unfused actors: the dense window ring)
+            only = (maddpg.actors.fusable(env, self.patch) and getattr(maddpg.actors, "arch", "") == "mlp"
+                    and env.device.type == "cuda")
+            self.rollout = Rollout(env, maddpg.actors, replay_slots=slots, training=True, seed=seed,
+                                   patch=self.patch, desc_ring="only" if only else False)
+        else:
+            fusable = maddpg.actors.fusable(env)
+            self.rollout = Rollout(env, maddpg.actors, replay_slots=slots, training=True, seed=seed,
+                                   obs_async="lazy" if fusable else False,
+                                   desc_ring=fusable and env.device.type == "cuda")
         self.learning_delay = learning_delay
         self.updates_per_step = updates_per_step
         # graph="launches" (default): the update re-issued as its recorded launches where every
