@@ -165,6 +165,31 @@ gw_status gw_fear_regret_accum(const double *fear_alt, const double *fear, const
 gw_status gw_feal_accum(const double *feal, const uint8_t *active, int64_t E, int32_t N, double *totals,
                         int64_t *steps, int64_t *envs, void *stream);
 
+/* Responsibility maps: one step's N x N valid-action sets binned by the cells the agents stood on.
+ * resp_valid [E][N][N][2] u16 as gw_set_fear_full stores it ([0]: the affected agent's 9-bit valid set with
+ * the actor on its MdR, [1]: under the actual actions; 4-byte aligned), cells [N][E] i32 the step's PRE-move
+ * cells (the env's pos layout: gw_copy_state with only pos set, before the gw_step), active [E] u8 or NULL
+ * (only the envs with active[e] != 0), counts [2][HW][10][10] u64 and visits [HW] u64 (may be NULL), both
+ * ADDED to (8-byte aligned; the caller zeroes them once).  For every such env e and ordered pair i != j, with
+ * vm = popc(resp_valid[e][i][j][0] & 0x1FF), va = popc(resp_valid[e][i][j][1] & 0x1FF):
+ *   counts[0][cells[i][e]][vm][va] += 1    "caused here": the actor's cell;
+ *   counts[1][cells[j][e]][vm][va] += 1    "received here": the affected agent's cell;
+ *   visits[cells[i][e]] += 1               once per (e, i).
+ * resp_full[e][i][j] == T[vm][va] (the Resp table, csrc/resp_tables.h), so the sum of Resp caused at cell c is
+ * sum_vm sum_va counts[0][c][vm][va] * T[vm][va], formed on the host in that fixed order
+ * (marlnav.resp_map_from_counts).  The device only counts: integer addition is exact, so the result is the
+ * same bit for bit whatever order the increments arrive in, a graph replay equals the eager run, and several
+ * ranks all-reduce the integers.  (A per-cell sum of doubles by atomics would depend on arrival order.)
+ * Every cell is clamped to [0, HW) and every popcount to [0, 9] before it indexes anything (csrc/resp_map.h,
+ * the same text the CPU check runs).  One launch of 256-thread blocks, one thread per (i, j, e) with e
+ * fastest, one 4-byte load of the pair of sets per thread, 64-bit global atomic adds without return; no LDS,
+ * no allocation, no host sync: graph-capturable.  Call it after the FeAR fence, and before gw_eval_accum in
+ * an evaluation step.  It has no env handle and so no gw_profile_spans kind.
+ * GW_ERR_ARG (with a gw_last_error message): NULL resp_valid, cells or counts; N outside 2..8; E <= 0 or
+ * HW <= 0; a misaligned pointer. */
+gw_status gw_resp_map_accum(const uint16_t *resp_valid, const int32_t *cells, const uint8_t *active,
+                            uint64_t *counts, uint64_t *visits, int32_t E, int32_t N, int32_t HW, void *stream);
+
 /* The responsibility shield: replace an RL action whose previewed FeAR exceeds tau, before the world moves.
  * fear_alt [E][K][9] f64 (gw_fear_preview's table for the proposed joint action), actions_in / actions_out
  * [E][K] i32 (may be the same buffer), mask [E][K] u16 9-bit action masks (NULL: all nine), probs

@@ -31,6 +31,10 @@ def main(argv=None):
     ap.add_argument("--resp-full", action="store_true",
                     help="also print the N x N responsibility matrix (every world agent as actor, the scripted "
                          "ones included) summed over the evaluation; runs the env with FeAR on")
+    ap.add_argument("--resp-map", nargs="?", const="", default=None, metavar="FILE.npz",
+                    help="also print two H x W responsibility maps: the mean Resp an agent standing on a cell "
+                         "caused to the others per visit, and the mean Resp it received there; runs the env with "
+                         "FeAR on.  With a file name, save counts, visits and the maps there (numpy .npz)")
     ap.add_argument("--shield", type=float, default=None, metavar="TAU",
                     help="responsibility shield: before every step, replace an RL action whose previewed FeAR "
                          "exceeds TAU by an allowed one (the most probable under the actor); also prints how many "
@@ -59,9 +63,11 @@ def main(argv=None):
         m = MADDPG(sc.K, sc.H, sc.W, arch=args.arch, device=torch.device("cuda"))
         m.load(args.checkpoint)
         actors = m.actors
-    r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps, fear=args.feal or args.resp_full,
+    resp_map = args.resp_map is not None
+    r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps,
+                 fear=args.feal or args.resp_full or resp_map,
                  seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield,
-                 shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps)
+                 shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps, resp_map=resp_map)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
@@ -78,6 +84,18 @@ def main(argv=None):
         print(f"Responsibility matrix (actor i -> agent j) summed over {r['steps']} env-steps:")
         for row in r["resp_full"].tolist():
             print("  " + " ".join(f"{v:12.6f}" for v in row))
+    if resp_map:
+        import numpy as np
+        maps, visits = r["resp_map"].numpy(), r["resp_map_visits"].numpy().reshape(sc.H, sc.W)
+        mean = maps / np.maximum(visits, 1)  # a cell nobody stood on has no pair-steps either: 0 / 1
+        for title, m in (("caused", mean[0]), ("received", mean[1])):
+            print(f"Mean Resp {title} per visit, by cell ({sc.H} x {sc.W}; '.': never visited):")
+            for y in range(sc.H):
+                print("  " + " ".join(f"{m[y, x]:7.4f}" if visits[y, x] else "      ." for x in range(sc.W)))
+        if args.resp_map:
+            np.savez(args.resp_map, counts=r["resp_map_counts"].numpy(), visits=visits, resp_map=maps,
+                     mean_caused=mean[0], mean_received=mean[1])
+            print(f"Responsibility maps saved to {args.resp_map}")
 
 
 if __name__ == "__main__":

@@ -1,1 +1,8 @@
 """MI355X-native vectorised MARL responsible-navigation grid world (host side)."""
+
+
+def __getattr__(name):  # marlnav.resp_map_from_counts / marlnav.resp_table, imported on first use
+    if name in ("resp_map_from_counts", "resp_table"):
+        from . import resp_map
+        return getattr(resp_map, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -31,7 +31,7 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
              fear: bool = False, seed: int = 42, record_actions: bool = False, fused: bool | None = None,
              variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False,
              feal: bool = False, resp_full: bool = False, shield: float | None = None,
-             shield_mode: str = "unilateral", shield_sweeps: int = 2) -> dict:
+             shield_mode: str = "unilateral", shield_sweeps: int = 2, resp_map: bool = False) -> dict:
     """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
     matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
     restricted agent j) summed over the episodes still running and divided by "steps".
@@ -45,6 +45,12 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
     responsibility matrix with every world agent as actor (StepResult.resp_full: how much agent i, RL or
     scripted, restricted agent j) over the episodes still running (f64 CPU tensor; divide by "steps" for
     the mean per env-step), and "resp_full_steps", the batched steps it covers.
+    resp_map (with ``fear=True``): the result also carries the responsibility maps of the episodes still
+    running (gw_resp_map_accum with the ``active`` mask of the other folds, on the cells copied before each
+    step): "resp_map" [2, H, W] f64 (plane 0: the Resp summed at the cell of the agent that caused it, plane
+    1: at the cell of the agent that received it), "resp_map_counts" (int64 [2, H*W, 10, 10], the exact counts
+    per cell and valid-action counts (vm, va) the map is formed from) and "resp_map_visits" (int64 [H*W],
+    agent-steps per cell): ``resp_map.reshape(2, -1) / resp_map_visits`` is the mean per visit.
     shield (a float tau; None: off): the responsibility shield at inference time.  Every step runs actor,
     ``env.fear_preview`` of the proposed actions, ``env.fear_shield`` (the env's action mask, the actor's
     probabilities, every RL agent shielded), then ``env.step`` with the shielded actions; works with
@@ -65,13 +71,15 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         raise ValueError("evaluate(feal=True) needs fear=True")
     if resp_full and not fear:
         raise ValueError("evaluate(resp_full=True) needs fear=True")
+    if resp_map and not fear:
+        raise ValueError("evaluate(resp_map=True) needs fear=True")
     sc = builtin(scenario) if isinstance(scenario, str) else scenario
     if fused is None:
         fused = actors.fusable(SimpleNamespace(K=sc.K, H=sc.H, W=sc.W))
     # the fused actor reads the obs descriptors: no dense obs is written at all
     env = VecGridEnv(sc, num_envs=episodes, fear=fear, max_steps=max_steps, auto_reset=False, seed=seed,
                      obs=not fused, variant=variant, fear_rows=resp_matrix, fear_alt=fear_regret, feal=feal,
-                     fear_full=resp_full)
+                     fear_full=resp_full or resp_map)
     try:
         obs, mask = env.reset()
         dev = env.device
@@ -87,6 +95,10 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         feal_cnt = torch.zeros(2, dtype=torch.int64, device=dev)  # calls, env-steps
         full = torch.zeros((env.N, env.N), dtype=torch.float64, device=dev) if resp_full else None
         full_calls = torch.zeros((), dtype=torch.int64, device=dev)
+        hw = env.H * env.W
+        map_counts = torch.zeros((2, hw, 10, 10), dtype=torch.int64, device=dev) if resp_map else None
+        map_visits = torch.zeros(hw, dtype=torch.int64, device=dev) if resp_map else None
+        map_cells = torch.empty((env.N, episodes), dtype=torch.int32, device=dev) if resp_map else None
         table = torch.empty((episodes, env.K, 9), dtype=torch.float64, device=dev) if shield is not None else None
         # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
         shield_cnt = torch.zeros((4 if joint_mode else 2, env.K), dtype=torch.int64, device=dev)
@@ -112,7 +124,11 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
                 shield_cnt[1] += ((flags >> 1) * on).sum(0)
             if record_actions:
                 recorded.append(actions.clone())
+            if resp_map:  # the step's pre-move cells
+                env.copy_pos(map_cells)
             r = env.step(actions)
+            if resp_map:  # the active envs' sets binned by cell, likewise before the done ones are retired
+                env.resp_map_accum(r.resp_valid, map_cells, map_counts, map_visits, active=active)
             if resp_matrix:  # the active envs' Resp rows, before gw_eval_accum retires the done ones
                 _lib.check(lib.gw_fear_row_accum(r.fear_row.data_ptr(), active.data_ptr(), episodes, env.K, env.N,
                                                  resp.data_ptr(), resp_calls.data_ptr(),
@@ -152,6 +168,10 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             out["feal"] = (feal_sum / max(c[2], 1)).cpu()
         if resp_full:
             out["resp_full"], out["resp_full_steps"] = full.cpu(), int(full_calls)
+        if resp_map:
+            from .resp_map import resp_map_from_counts
+            out["resp_map_counts"], out["resp_map_visits"] = map_counts.cpu(), map_visits.cpu()
+            out["resp_map"] = resp_map_from_counts(out["resp_map_counts"])[0].reshape(2, env.H, env.W)
         if shield is not None:
             out["shield_replaced"], out["shield_stuck"] = shield_cnt[0].cpu(), shield_cnt[1].cpu()
             if joint_mode:

@@ -212,7 +212,8 @@ class Rollout:
                  obs_async: bool | str = False, fear_async: bool = False, gather=None, patch: int = 0,
                  patch_async: bool | None = None, desc_ring: bool | str = False, resp_matrix: bool = False,
                  fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
-                 shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2):
+                 shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2,
+                 resp_map: bool = False):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -260,6 +261,15 @@ class Rollout:
         (StepResult.resp_full, every world agent as actor) is summed over the envs into a running [N, N]
         total (gw_fear_row_accum with K = N, one launch per step, also inside ``capture`` graphs);
         ``totals()`` then carries "resp_full" and "resp_full_steps".
+        resp_map (an env built with ``fear_full=True``; turns ``resp_full`` on): where on the grid the agents
+        restrict each other.  The agents' cells are copied before every step (``env.copy_pos``, N * E int32)
+        and the step's valid-action sets are binned by them after the FeAR fence, where ``resp_full`` is
+        folded (gw_resp_map_accum, one launch per step, also inside ``capture`` graphs, under the rule
+        ``resp_full`` follows there); ``totals()`` then carries "resp_map_counts" (int64 [2, H*W, 10, 10]:
+        plane 0 caused at the actor's cell, plane 1 received at the affected agent's cell), "resp_map_visits"
+        (int64 [H*W], agent-steps per cell) and the derived "resp_map" ([2, H, W] f64, the summed Resp per
+        cell: ``marlnav.resp_map_from_counts``).  The device keeps integer counts, so the totals are the same
+        bit for bit eager or replayed, and several ranks all-reduce the integers.
         shield (a float tau; None: off, no extra launch): the responsibility shield.  Every step runs actor,
         then ``env.fear_preview`` of the proposed actions, then ``env.fear_shield`` (the env's action mask, the
         actor's probabilities, every RL agent shielded), then ``env.step`` with the shielded actions.  The ring
@@ -364,6 +374,15 @@ class Rollout:
                 raise ValueError("Rollout(feal=True) needs VecGridEnv(feal=True)")
             self._feal = torch.zeros(env.N, dtype=torch.float64, device=env.device)
             self._feal_cnt = torch.zeros(2, dtype=torch.int64, device=env.device)  # steps, env-steps
+        self._map_counts = self._map_visits = self._map_cells = None
+        if resp_map:
+            if env.out.get("resp_valid") is None:
+                raise ValueError("Rollout(resp_map=True) needs VecGridEnv(fear_full=True)")
+            resp_full = True
+            hw = env.H * env.W
+            self._map_counts = torch.zeros((2, hw, 10, 10), dtype=torch.int64, device=env.device)
+            self._map_visits = torch.zeros(hw, dtype=torch.int64, device=env.device)
+            self._map_cells = torch.empty((env.N, env.E), dtype=torch.int32, device=env.device)
         self._full = self._full_steps = None
         if resp_full:
             if env.out.get("resp_full") is None:
@@ -452,6 +471,8 @@ class Rollout:
                                                  self._full.data_ptr(), self._full_steps.data_ptr(),
                                                  torch.cuda.current_stream(env.device).cuda_stream),
                        "gw_fear_row_accum")
+        if self._map_counts is not None:  # the step's sets (FeAR-owned) binned by the cells copied before it
+            self.env.resp_map_accum(self.env.out["resp_valid"], self._map_cells, self._map_counts, self._map_visits)
         if self.gather is not None:
             self.gather.push()  # the step wrote ep_return / done into the gather's send buffer
         if self._acc is not None:
@@ -601,6 +622,8 @@ class Rollout:
         if self.shield is not None:  # beside the previous step's FeAR kernels (the preview has its own record buffer)
             actions = self._shielded(actions, probs, mask)
         self._flush()  # after the actor: it overlapped the previous step's FeAR kernel
+        if self._map_cells is not None:  # this step's pre-move cells (the previous step's are folded by now)
+            env.copy_pos(self._map_cells)
         if self.replay is not None:
             rp = self.replay
             nxt = (self.t + 1) % rp.S
@@ -758,6 +781,9 @@ class Rollout:
         With ``resp_full``: "resp_full", the [N, N] sum of every step's and env's responsibility matrix
         (f64 CPU tensor, all-reduced with the rest), and "resp_full_steps", this rank's steps (like
         "resp_steps": the ranks step in lockstep, so the count is not summed over them).
+        With ``resp_map``: "resp_map_counts" (int64 [2, H*W, 10, 10] CPU tensor, summed over the ranks in an
+        integer all-reduce of its own), "resp_map_visits" (int64 [H*W]) and "resp_map" ([2, H, W] f64:
+        ``marlnav.resp_map_from_counts`` of the counts; plane 0 the Resp caused at a cell, plane 1 received).
         With ``shield``: "shield_replaced" [K] and "shield_stuck" [K] (int64 CPU tensors): the agent-steps whose
         action the shield replaced (flag bit 0) / that had no allowed action (flag bit 1).  With
         ``shield_mode="joint"`` also "shield_over" [K] (agent-steps whose applied action's FeAR exceeds tau, flag
@@ -815,6 +841,14 @@ class Rollout:
             N = self.env.N
             out["resp_full"] = local[nst:nst + N * N].reshape(N, N).cpu()
             out["resp_full_steps"] = int(self._full_steps)
+        if self._map_counts is not None:  # exact integer counts: their own all-reduce
+            cnt, vis = self._map_counts.clone(), self._map_visits.clone()
+            if self.distributed:
+                dist.all_reduce(cnt, group=self.group)
+                dist.all_reduce(vis, group=self.group)
+            from .resp_map import resp_map_from_counts
+            out["resp_map_counts"], out["resp_map_visits"] = cnt.cpu(), vis.cpu()
+            out["resp_map"] = resp_map_from_counts(out["resp_map_counts"])[0].reshape(2, self.env.H, self.env.W)
         out.update(shield)
         return out
 

@@ -542,6 +542,45 @@ class VecGridEnv:
         self.out["resp_full"], self.out["resp_valid"] = resp_full, resp_valid
         self._into_cache.clear()  # the cached StepResults carry the old views
 
+    def copy_pos(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The agents' current cells into ``out`` ([N, E] int32, the env's pos layout; default: a new tensor):
+        one device copy on the current stream (gw_copy_state with only pos set), capturable.  Called before
+        ``step`` it holds that step's pre-move cells, what ``resp_map_accum`` bins by."""
+        if out is None:
+            out = torch.empty((self.N, self.E), dtype=torch.int32, device=self.device)
+        if out.dtype != torch.int32 or out.numel() != self.N * self.E or not out.is_contiguous() or \
+                out.device != self.device:
+            raise ValueError(f"copy_pos: need a contiguous int32 tensor of {self.N * self.E} elements on {self.device}")
+        gs = _lib.GwState(pos=_ptr(out))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_copy_state(self.handle, C.byref(gs), 0, self._stream()), "gw_copy_state")
+        return out
+
+    def resp_map_accum(self, resp_valid: torch.Tensor, cells: torch.Tensor, counts: torch.Tensor,
+                       visits: torch.Tensor | None = None, active: torch.Tensor | None = None):
+        """Bin one step's N x N valid-action sets by the agents' pre-move cells (gw_resp_map_accum,
+        include/rollout_ops.h): for every env (``active[e] != 0`` if a mask is given) and ordered pair i != j,
+        ``counts[0, cells[i, e], vm, va] += 1`` (caused at the actor's cell), ``counts[1, cells[j, e], vm, va] += 1``
+        (received at the affected agent's cell) and ``visits[cells[i, e]] += 1`` once per (e, i).
+        resp_valid: [E, N, N, 2] int16 (StepResult.resp_valid); cells: [N, E] int32 (``copy_pos`` before the
+        step); counts: [2, H*W, 10, 10] int64 and visits: [H*W] int64 or None, both added to; active: [E] uint8
+        or None.  ``marlnav.resp_map_from_counts`` turns the counts into the maps.  Raises on an env created
+        without ``fear_full=True``."""
+        if self.out.get("resp_valid") is None:
+            raise ValueError("resp_map_accum needs VecGridEnv(fear_full=True) (the step's resp_valid sets)")
+        E, N, HW = self.E, self.N, self.H * self.W
+        for t, dt, n, name in ((resp_valid, torch.int16, 2 * E * N * N, "resp_valid"), (cells, torch.int32, N * E, "cells"),
+                               (counts, torch.int64, 2 * HW * 100, "counts"), (visits, torch.int64, HW, "visits"),
+                               (active, torch.uint8, E, "active")):
+            if t is None and name in ("visits", "active"):
+                continue
+            if t is None or t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"resp_map_accum({name}=...): need a contiguous {dt} tensor of {n} elements on "
+                                 f"{self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_resp_map_accum(_ptr(resp_valid), _ptr(cells), _ptr(active), _ptr(counts),
+                                                  _ptr(visits), E, N, HW, self._stream()), "gw_resp_map_accum")
+
     def fear_preview(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
                      out: torch.Tensor | None = None, actions: torch.Tensor | None = None,
                      mdr: torch.Tensor | None = None) -> torch.Tensor:
