@@ -1,7 +1,8 @@
-// cf_env.h -- internal: the device code that gridenv.hip shares with the translation units of its
-// wave-per-env FeAR kernels (fear_full.hip): the launch parameters, one world update in registers
-// (World, simulate, cf_valid), the step's FearRec, the cell table's bit layout, lds_fill and the CfEnv
-// scaffold.  gridenv.hip includes it where this code used to stand, so its own kernels compile as before.
+// cf_env.h -- internal: the device code that gridenv.hip shares with the translation units of the
+// counterfactual FeAR kernels (fear_cf.hip, fear_full.hip, fear_preview.hip, fear_shield_joint.hip,
+// fear_matrix.hip): the launch parameters, one world update in registers (World, simulate, cf_valid), the
+// step's FearRec, the cell table's bit layout, lds_fill, the CfEnv scaffold and those files' launchers, which
+// gridenv.hip calls.  gridenv.hip includes it where this code used to stand, so its own kernels compile as before.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -352,7 +353,7 @@ __device__ __forceinline__ void simulate(World<N, LIST> &w, const OK &okm, int K
     }
 }
 
-// One counterfactual world update of the wave-per-env kernels (fear_alt_kernel, feal_kernel): `pos`
+// One counterfactual world update of the wave-per-env kernels (fear_alt_core.h, feal_kernel, fear_full_kernel): `pos`
 // under the joint action `joint`, no apples (APPLES is dead: K = 0).  Returns the N-bit set of agents
 // that end valid (neither crashed nor restricted).  LIST: wl_row is the lane's World::lw row.  fear_task
 // and fear_matrix_kernel keep this block in place (why: profiles/fear_scaffold/SUMMARY.md).
@@ -457,7 +458,8 @@ __device__ __forceinline__ void lds_fill(uint32_t *dst, const uint32_t *__restri
 }
 
 // ---------------------------------------------------------------------------------------
-// CfEnv: the wave-per-env scaffold of fear_alt_kernel, feal_kernel and fear_full_kernel.  All run counterfactual
+// CfEnv: the wave-per-env scaffold of fear_alt_kernel, feal_kernel (fear_cf.hip), fear_full_kernel (fear_full.hip)
+// and fear_shield_joint_kernel (fear_shield_joint.hip; the first and the last share fear_alt_core.h).  All run counterfactual
 // world updates from the step's FearRec (pre-step cells, joint action): one wave per env, CF_WAVES
 // envs per block, the env's tasks dealt to the wave's lanes round-robin, one register-resident world
 // update (cf_valid) per lane and turn.  A task ORs valid bits into the kernel's 9-bit sets in LDS
@@ -540,5 +542,31 @@ struct ShieldJointArgs {
 // gwprof::launch, from the record in p.fwork
 hipError_t launch_fear_shield_joint(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
                                     const ShieldJointArgs &a);
+
+// fear_alt_kernel<N> (fear_cf.hip; gw_set_fear_alt, and gw_fear_preview on the preview's record) over p's env
+// range on s, through gwprof::launch: table [E][K][9]
+hipError_t launch_fear_alt(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p, double *table);
+
+// feal_kernel<N> (fear_cf.hip, gw_set_feal) over p's env range on s, through gwprof::launch
+hipError_t launch_feal(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p, double *feal,
+                       uint16_t *feal_valid);
+
+// gw_fear_matrix's arguments: n world snapshots the caller supplies
+struct FmParams {
+    const uint32_t *celltab;
+    const double *tab;        // [0, 100) Resp(vm, va), [100, 200) FeAL(vm, va)
+    int HW, W;
+    uint32_t w_magic;
+    const int32_t *cells, *acts, *mdr;  // [n][N]; mdr may be null (the cells' MdR)
+    const uint8_t *in_list;             // [n] bit a: agent a in ActionID4Agents; null = all
+    double *resp;                       // [n][N][N]
+    int32_t *vm, *va;                   // [n][N][N] or null
+    double *feal;                       // [n][N] or null
+    int32_t *feal_vm, *feal_va;         // [n][N] or null
+};
+
+// fear_matrix_kernel<N> (fear_matrix.hip, gw_fear_matrix): one block per snapshot on s, through gwprof::launch;
+// dyn: the cell table's bytes.  N = 1 is an error
+hipError_t launch_fear_matrix(int N, int64_t n_blocks, size_t dyn, hipStream_t s, const FmParams &q);
 
 }  // namespace gw

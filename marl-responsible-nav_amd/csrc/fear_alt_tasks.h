@@ -1,4 +1,5 @@
-// fear_alt_tasks.h — task-list arithmetic of fear_alt_kernel (csrc/gridenv.hip, gw_set_fear_alt).
+// fear_alt_tasks.h — task-list arithmetic of the per-action FeAR table (csrc/fear_alt_core.h: fear_alt_kernel in
+// fear_cf.hip, fear_shield_joint_kernel in fear_shield_joint.hip).
 //
 // Pure integer functions, host and device, so that a stand-alone CPU program can check them
 // (tools/fear_alt_tasks_check.cpp).  Per env and RL actor k with close count c (k included), the
@@ -51,6 +52,30 @@ FA_HD Task decode(int r, int c) {
 
 FA_HD constexpr int encode(int a, int slot, int bi, int c) {
     return a * per_variant(c) + (slot < 0 ? 0 : 1 + 8 * slot + bi);
+}
+
+struct Actor {
+    int k;  // the actor
+    int r;  // its task, 0..tcount[k]-1
+};
+
+// task ti of a run over the actors in `sel`, whose tasks follow each other in ascending actor order (tcount[q]
+// tasks of actor q): the actor and its task.  ti at or past the selected total: actor N - 1 with r past its last
+// task (decode clamps it), so every index built from the result stays in range.  N - 1 steps, no bound read from data
+template <int N>
+FA_HD Actor actor_of(uint32_t sel, const int (&tcount)[N], int ti) {
+    Actor t{0, ti};
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+    for (int q = 0; q < N - 1; ++q) {  // k moves on past q while the task lies behind q's (none if q is not selected)
+        const int tc = ((sel >> q) & 1u) ? tcount[q] : 0;
+        if (q == t.k && t.r >= tc) {
+            t.r -= tc;
+            ++t.k;
+        }
+    }
+    return t;
 }
 
 // the bi-th action other than `own` (0..8): the 8 alternatives in ascending order

@@ -1,7 +1,8 @@
 // fear_preview.hip -- preview_rec_kernel (gw_fear_preview): the FearRec of the step the next gw_step will run,
 // built from the env's current state without moving the world.  A translation unit of its own on the shared
 // headers (cf_env.h, draw_action.h), so that the code object of gridenv.hip's step kernels does not change with
-// it; gridenv.hip owns the preview's record buffer and runs fear_alt_kernel on it right behind this kernel.
+// it; gridenv.hip owns the preview's record buffer and runs fear_alt_kernel (fear_cf.hip) on it right behind this
+// kernel.
 #include <hip/hip_runtime.h>
 
 #include "cf_env.h"

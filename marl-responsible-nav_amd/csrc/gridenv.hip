@@ -40,7 +40,7 @@
 #include "fear_alt_tasks.h"
 #include "resp_tables.h"
 #include "cf_env.h"
-#include "np_sum.h"  // np_sum_row (shared with fear_shield_joint.hip)
+#include "np_sum.h"  // np_sum_row (shared with fear_alt_core.h)
 
 namespace gw {
 
@@ -1475,265 +1475,6 @@ __global__ void __launch_bounds__(GW_FEAR_T) fear_delta_kernel(Params p, float *
     obs_delta_block(p, obs, saved, blockIdx.x - nfear);
 }
 
-// ---------------------------------------------------------------------------------------
-// fear_alt_kernel (gw_set_fear_alt): the per-action counterfactual FeAR table of a step,
-//   fear_alt[e][k][a] = np.sum(Resp) of FeAR_4_one_actor(actor = k) with k playing a,
-// from the step's FearRec, on the wave-per-env scaffold (CfEnv).  The env's tasks are those of
-// csrc/fear_alt_tasks.h: per actor 9 variants x (1 base + 8 alternatives of each close agent).
-// A sim ORs the affected agent's valid bit into the 9-bit set vb[k][a][j] (bit b = j valid under
-// its action b; the base sim supplies bit act[j], and all nine bits of an agent outside the close
-// set, which stays: 9 * valid(base) as fear_record); popcounts give the V counts.  The MdR variant
-// is one of the nine, so Resp[k][j](a) = tab[V(mdr[k], j)][V(a, j)], summed by np_sum_row.
-// ---------------------------------------------------------------------------------------
-template <int N>
-__global__ void __launch_bounds__(CF_T) fear_alt_kernel(Params p, double *__restrict__ table) {
-    constexpr bool LIST = N >= GW_LIST_MIN_N;
-    constexpr int VBW = fear_alt::bit_words(N, N);  // per env, sized for K = N
-    static_assert(fear_alt::max_per_env(4, 2) == 450 && fear_alt::max_per_env(8, 2) == 1026, "task maxima");
-    static_assert(VBW == N * NA * N && VBW <= 576, "valid-bit sets: [K <= N][9][N] words per env");
-    static_assert(fear_alt::max_per_env(N, N) <= 4104, "tasks per env fit an int with room");
-    __shared__ uint32_t vb[CF_WAVES][VBW];
-    __shared__ uint2 wl[LIST ? CF_T * N : 1];  // World<N, true> rows (one per thread)
-    __shared__ unsigned int s_nsim;
-    static_assert(sizeof(uint32_t) * CF_WAVES * VBW + sizeof(uint2) * (LIST ? CF_T * N : 1) <= 26 * 1024,
-                  "static LDS of fear_alt_kernel");
-    CfEnv<N> c;
-    c.begin(p, 0, s_nsim, [&] { for (int i = c.lane; i < VBW; i += 64) vb[c.wave][i] = 0u; });
-    const int (&pos)[N] = c.pos, (&act)[N] = c.act, (&mdr)[N] = c.mdr;
-    const int tid = threadIdx.x, wave = c.wave, lane = c.lane, K = min(p.K, N);
-    const CtabOk okv{c.ctab};
-    // close sets and task counts of the actors, in registers
-    uint32_t close[N];
-    int tcount[N], ntask = 0;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        close[k] = 0u;
-        tcount[k] = 0;
-        if (k >= K) continue;
-#pragma unroll
-        for (int n = 0; n < N; ++n)
-            if (n == k || manhattan(p, pos[k], pos[n]) <= 5) close[k] |= 1u << n;
-        tcount[k] = fear_alt::per_actor(__popc(close[k]));  // popc in 1..N: at most 9 (1 + 8 (N - 1))
-        ntask += tcount[k];
-    }
-    if (!c.live) ntask = 0;
-
-    for (int ti = lane; ti < ntask; ti += 64) {
-        // (actor k, task r of k): the actors' tasks follow each other
-        int k = 0, r = ti;
-#pragma unroll
-        for (int q = 0; q < N - 1; ++q)
-            if (q == k && q < K - 1 && r >= tcount[q]) {
-                r -= tcount[q];
-                ++k;
-            }
-        uint32_t cl = 0u;
-#pragma unroll
-        for (int q = 0; q < N; ++q)
-            if (q == k) cl = close[q];
-        const fear_alt::Task tk = fear_alt::decode(r, __popc(cl));
-        const int j = tk.slot < 0 ? -1 : fear_alt::nth_agent(cl & ~(1u << k), tk.slot);
-        int joint[N], b = 0;
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-            joint[n] = ((cl >> n) & 1u) ? act[n] : 0;
-            if (n == k) joint[n] = tk.a;
-            if (n == j) joint[n] = b = fear_alt::alternative(tk.bi, act[n]);
-        }
-        const uint32_t valid = cf_valid<N, LIST, true>(p.W, p.w_magic, okv, pos, joint, LIST ? &wl[tid * N] : nullptr);
-        uint32_t *row = &vb[wave][(k * NA + tk.a) * N];
-        if (j >= 0) {
-            if ((valid >> j) & 1u) atomicOr(&row[j], 1u << b);
-        } else {
-#pragma unroll
-            for (int n = 0; n < N; ++n)
-                if (n != k && ((valid >> n) & 1u)) atomicOr(&row[n], ((cl >> n) & 1u) ? (1u << act[n]) : 0x1FFu);
-        }
-    }
-    c.end(p, s_nsim, ntask);
-    if (!c.live) return;
-    // (k, a) per lane: V counts -> Resp table -> np.sum of the row in numpy's order
-    for (int i = lane; i < K * NA; i += 64) {
-        const int k = i / NA, a = i - k * NA;
-        int mk = 0;
-#pragma unroll
-        for (int q = 0; q < N; ++q)
-            if (q == k) mk = mdr[q];
-        const uint32_t *rm = &vb[wave][(k * NA + mk) * N], *ra = &vb[wave][(k * NA + a) * N];
-        double resp[N];
-#pragma unroll
-        for (int jj = 0; jj < N; ++jj) {
-            const int vm = __popc(rm[jj] & 0x1FFu), va = __popc(ra[jj] & 0x1FFu);
-            resp[jj] = (jj == k) ? 0.0 : c.tab[vm * 10 + va];
-        }
-        table[(c.e * p.K + k) * NA + a] = np_sum_row<N>(resp, k);
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// feal_kernel (gw_set_feal): Responsibility.FeAL (custom/Responsibility.py:213-303) of a step for
-// every world agent i, from the step's FearRec (pre-step cells, joint action; every agent listed):
-//   feal[e][i] = T[vm][va],  vm / va = agent i's valid moves (neither crashed nor restricted,
-//   CountValidMovesOfAffected :16-54) over its nine actions b while every other agent plays its
-//   MdR / its actual action; the two 9-bit sets go to valid[e][i][0 / 1].
-// On the wave-per-env scaffold (CfEnv), with the FeAL table T in the Resp table's place.  Tasks
-// [0, 9 N): (i, others actual, b); then 9 per agent whose two variants differ: (i, others MdR, b).
-// The variants of i coincide when every other agent's action is its MdR (diff & ~(1 << i) == 0,
-// the same in every lane of the wave): that agent's MdR set is a copy of its actual set.
-// A task ORs bit b into the set (i, v) in LDS; after the barrier lane i counts and looks T up.
-// ---------------------------------------------------------------------------------------
-template <int N>
-__global__ void __launch_bounds__(CF_T) feal_kernel(Params p, double *__restrict__ feal,
-                                                    uint16_t *__restrict__ valid_out) {
-    constexpr bool LIST = N >= GW_LIST_MIN_N;
-    constexpr int MAXT = 2 * NA * N;  // tasks per env at most
-    static_assert(MAXT <= 144, "18 N tasks per env: at most 3 turns of a wave");
-    __shared__ uint32_t vb[CF_WAVES][2 * N];  // [i][v]: 9-bit valid sets, v = 0 others MdR, 1 others actual
-    __shared__ uint2 wl[LIST ? CF_T * N : 1];  // World<N, true> rows (one per thread)
-    __shared__ unsigned int s_nsim;
-    static_assert(sizeof(uint32_t) * CF_WAVES * 2 * N + sizeof(uint2) * (LIST ? CF_T * N : 1) <= 17 * 1024,
-                  "static LDS of feal_kernel");
-    CfEnv<N> c;
-    c.begin(p, 100, s_nsim, [&] { if (c.lane < 2 * N) vb[c.wave][c.lane] = 0u; });
-    const int (&pos)[N] = c.pos, (&act)[N] = c.act, (&mdr)[N] = c.mdr;
-    const int tid = threadIdx.x, wave = c.wave, lane = c.lane;
-    const CtabOk okv{c.ctab};
-    uint32_t diff = 0u;  // agents whose action is not their MdR
-#pragma unroll
-    for (int n = 0; n < N; ++n) diff |= (uint32_t)(act[n] != mdr[n]) << n;
-    uint32_t need = 0u;  // agents whose others-MdR variant is a world of its own
-#pragma unroll
-    for (int i = 0; i < N; ++i) need |= (uint32_t)((diff & ~(1u << i)) != 0u) << i;
-    const int ntask = c.live ? NA * (N + __popc(need)) : 0;  // <= MAXT, from registers
-
-    for (int ti = lane; ti < min(ntask, MAXT); ti += 64) {
-        const int g = ti / NA, b = ti - g * NA;
-        const bool actual = g < N;
-        int i = actual ? g : fear_alt::nth_agent(need, g - N);
-        i = min(max(i, 0), N - 1);
-        int joint[N];
-#pragma unroll
-        for (int n = 0; n < N; ++n) joint[n] = (n == i) ? b : (actual ? act[n] : mdr[n]);
-        const uint32_t valid = cf_valid<N, LIST, false>(p.W, p.w_magic, okv, pos, joint, LIST ? &wl[tid * N] : nullptr);
-        if ((valid >> i) & 1u) atomicOr(&vb[wave][2 * i + (actual ? 1 : 0)], 1u << b);
-    }
-    c.end(p, s_nsim, ntask);
-    if (!c.live || lane >= N) return;
-    const uint32_t va_set = vb[wave][2 * lane + 1] & 0x1FFu;
-    const uint32_t vm_set = ((need >> lane) & 1u) ? (vb[wave][2 * lane] & 0x1FFu) : va_set;
-    if (feal) feal[c.e * N + lane] = c.tab[__popc(vm_set) * 10 + __popc(va_set)];
-    // the pair [0] others MdR, [1] others actual as one 4-byte store (gw_set_feal checks the alignment)
-    if (valid_out) reinterpret_cast<uint32_t *>(valid_out)[c.e * N + lane] = vm_set | (va_set << 16);
-}
-
-// ---------------------------------------------------------------------------------------
-// Responsibility.FeAR (custom/Responsibility.py:57-132, every agent as actor) and FeAL
-// (:213-303) for n world snapshots, one 128-thread block per snapshot.  Every world update the
-// two need is one task (9 per group):  "act" groups jj = 0..N-1 (the action list unchanged,
-// agent jj's 9 actions: ValidMoves_action[.][jj] and FeAL's action count of jj), "MdR" groups
-// (ii, jj != ii) (actor ii swapped to its MdR: ValidMoves_moveDeRigueur[ii][jj]) and "FeAL"
-// groups ii (every other listed agent swapped to its MdR).  Agents outside the action list
-// stay and ignore swaps (SwapActionIDs4Agents, grid_world.py:709-726).  Valid-move bits are
-// OR-ed into LDS, counted, and mapped through exact host-computed f64 tables.
-// ---------------------------------------------------------------------------------------
-struct FmParams {
-    const uint32_t *celltab;
-    const double *tab;        // [0, 100) Resp(vm, va), [100, 200) FeAL(vm, va)
-    int HW, W;
-    uint32_t w_magic;
-    const int32_t *cells, *acts, *mdr;  // [n][N]; mdr may be null (the cells' MdR)
-    const uint8_t *in_list;             // [n] bit a: agent a in ActionID4Agents; null = all
-    double *resp;                       // [n][N][N]
-    int32_t *vm, *va;                   // [n][N][N] or null
-    double *feal;                       // [n][N] or null
-    int32_t *feal_vm, *feal_va;         // [n][N] or null
-};
-
-template <int N>
-__global__ void __launch_bounds__(128) fear_matrix_kernel(FmParams q) {
-    constexpr int T = 128, NG = N + N * (N - 1) + N;
-    extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
-    uint32_t *ctab = reinterpret_cast<uint32_t *>(dyn);
-    __shared__ int s_loc[N], s_act[N], s_mdr[N];
-    __shared__ uint32_t s_bits[NG];  // 9-bit valid masks per group
-    __shared__ uint32_t s_in;
-    const int tid = threadIdx.x;
-    const int64_t e = blockIdx.x;
-    lds_fill<T>(ctab, q.celltab, q.HW, tid);
-    for (int g = tid; g < NG; g += T) s_bits[g] = 0;
-    if (tid < N) {
-        const int c = q.cells[e * N + tid];
-        const int a = q.acts[e * N + tid];
-        s_loc[tid] = ((unsigned)c < (unsigned)q.HW) ? c : 0;
-        s_act[tid] = ((unsigned)a < (unsigned)NA) ? a : 0;
-    }
-    if (tid == 0) s_in = q.in_list ? (uint32_t)q.in_list[e] : 0xFFu;
-    __syncthreads();
-    if (tid < N) {
-        const int m = q.mdr ? q.mdr[e * N + tid] : (int)((ctab[s_loc[tid]] >> CT_MDR) & 0xFu);
-        s_mdr[tid] = ((unsigned)m < (unsigned)NA) ? m : 0;
-    }
-    __syncthreads();
-    const uint32_t in = s_in;
-    const CtabOk okv{ctab};
-    for (int t = tid; t < 9 * NG; t += T) {
-        const int g = t / 9, b = t - 9 * (t / 9);
-        int joint[N], loc[N], fin[N];
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-            loc[n] = s_loc[n];
-            joint[n] = ((in >> n) & 1u) ? s_act[n] : 0;  // defaultAction 'stay' for the unlisted
-        }
-        int affected;
-        if (g < N) {  // action list unchanged
-            affected = g;
-        } else if (g < N + N * (N - 1)) {  // actor ii -> MdR
-            const int idx = g - N, ii = idx / (N - 1), r = idx - ii * (N - 1);
-            affected = r + (r >= ii);
-#pragma unroll
-            for (int n = 0; n < N; ++n)
-                if (n == ii && ((in >> n) & 1u)) joint[n] = s_mdr[n];
-        } else {  // everybody but ii -> MdR (FeAL)
-            affected = g - N - N * (N - 1);
-#pragma unroll
-            for (int n = 0; n < N; ++n)
-                if (n != affected && ((in >> n) & 1u)) joint[n] = s_mdr[n];
-        }
-#pragma unroll
-        for (int n = 0; n < N; ++n)
-            if (n == affected && ((in >> n) & 1u)) joint[n] = b;
-        // cf_valid's block in place (profiles/fear_scaffold/SUMMARY.md)
-        int apple[MAXN];
-#pragma unroll
-        for (int k = 0; k < MAXN; ++k) apple[k] = -1;
-        World<N> w;
-        w.init(loc, joint, q.W, q.w_magic);
-        uint32_t caught;
-        simulate<N, false>(w, okv, 0, apple, caught, fin);
-        if (!(((w.crash | w.restr) >> affected) & 1u)) atomicOr(&s_bits[g], 1u << b);
-    }
-    __syncthreads();
-    if (tid < N * N) {
-        const int ii = tid / N, jj = tid - ii * N;
-        int m = 0, a = 0;
-        double r = 0.0;
-        if (ii != jj) {
-            m = __popc(s_bits[N + ii * (N - 1) + (jj - (jj > ii))]);
-            a = __popc(s_bits[jj]);
-            r = q.tab[m * 10 + a];
-        }
-        q.resp[e * N * N + tid] = r;
-        if (q.vm) q.vm[e * N * N + tid] = m;
-        if (q.va) q.va[e * N * N + tid] = a;
-    }
-    if (tid < N) {
-        const int m = __popc(s_bits[N + N * (N - 1) + tid]), a = __popc(s_bits[tid]);
-        if (q.feal) q.feal[e * N + tid] = q.tab[100 + m * 10 + a];
-        if (q.feal_vm) q.feal_vm[e * N + tid] = m;
-        if (q.feal_va) q.feal_va[e * N + tid] = a;
-    }
-}
-
 }  // namespace gw
 
 // =========================================================================================
@@ -2121,8 +1862,9 @@ int64_t ceil_div(int64_t n, int64_t d) { return (n + d - 1) / d; }
 // C2's step kernel slower: 11.4 -> 12.2 us, profiles/r3_c2.)
 size_t step_lds(const gw::Params &p, bool fear) { return (size_t)p.resp_off + (fear ? 100 * sizeof(double) : 0); }
 
-// dynamic LDS of the FeAR kernels (fear_v2, fear_rows_kernel, fear_alt_kernel, feal_kernel):
-// [cell table][Resp] (feal_kernel: the FeAL table in Resp's place).
+// dynamic LDS of the FeAR kernels (fear_v2, fear_rows_kernel here; through launch_cf the wave-per-env kernels
+// of fear_cf.hip, fear_full.hip and fear_shield_joint.hip): [cell table][Resp] (feal_kernel: the FeAL table in
+// Resp's place).
 // Sets p's offsets for it and returns its size.
 size_t fear_lds(gw::Params &p) {
     p.lds_cdf = 0;
@@ -2211,17 +1953,9 @@ hipError_t launch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
     });
 }
 
-// gw_fear_matrix's kernel (N >= 2: the caller rejects N = 1, FeAR needs a second agent)
+// gw_fear_matrix's kernel (fear_matrix.hip; N >= 2: the caller rejects N = 1, FeAR needs a second agent)
 hipError_t launch_fear_matrix(const Env *env, int64_t n_blocks, const gw::FmParams &q, hipStream_t s) {
-    return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) -> hipError_t {
-        constexpr int N = decltype(n)::value;
-        if constexpr (N >= 2) {
-            gw_launch((gw::fear_matrix_kernel<N>), dim3((unsigned)n_blocks), dim3(128), (size_t)celltab_lds(env->HW), s, q);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    });
+    return gw::launch_fear_matrix(env->N, n_blocks, (size_t)celltab_lds(env->HW), s, q);
 }
 
 // obs_kernel's LDS: road bitmask, OBS_BE flags, [2][obs_be][K][N + 1] patch cells + values
@@ -2525,8 +2259,8 @@ gw_status step_fear_alt(Env *env, const gw::Params &p, hipStream_t s) {
         HIP_TRY(hipMemsetAsync(env->fear_alt, 0, sizeof(double) * (size_t)env->E * env->K * GW_N_ACTIONS, s));
         return GW_OK;
     }
-    return launch_cf(env, GW_SPAN_FEAR_ALT, p, [&](auto n, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
-        gw_launch((gw::fear_alt_kernel<decltype(n)::value>), grid, block, dyn, s, q, env->fear_alt);
+    return launch_cf(env, GW_SPAN_FEAR_ALT, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        (void)gw::launch_fear_alt(env->N, grid, block, dyn, s, q, env->fear_alt);
     });
 }
 
@@ -2534,8 +2268,8 @@ gw_status step_fear_alt(Env *env, const gw::Params &p, hipStream_t s) {
 // (armed only with FeAR on: the world update stored the FearRec)
 gw_status step_feal(Env *env, const gw::Params &p, hipStream_t s) {
     if (!feal_armed(env)) return GW_OK;
-    return launch_cf(env, GW_SPAN_FEAL, p, [&](auto n, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
-        gw_launch((gw::feal_kernel<decltype(n)::value>), grid, block, dyn, s, q, env->feal, env->feal_valid);
+    return launch_cf(env, GW_SPAN_FEAL, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        (void)gw::launch_feal(env->N, grid, block, dyn, s, q, env->feal, env->feal_valid);
     });
 }
 
@@ -3224,12 +2958,12 @@ gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t
     p.scripted = scripted;
     p.fwork = env->preview_rec;
     hipError_t rec = hipSuccess;
-    GW_TRY(launch_cf(env, GW_SPAN_FEAR_PREVIEW, p, [&](auto n, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
-        // the record builder (fear_preview.hip, its own code object), then the step's own table kernel on that
-        // record: both launches are the one span
+    GW_TRY(launch_cf(env, GW_SPAN_FEAR_PREVIEW, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        // the record builder (fear_preview.hip, its own code object), then the step's own table kernel
+        // (fear_cf.hip) on that record: both launches are the one span
         rec = gw::launch_preview_rec(env->N, s, q, actions, mdr);
         if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
-        gw_launch((gw::fear_alt_kernel<decltype(n)::value>), grid, block, dyn, s, q, fear_alt);
+        (void)gw::launch_fear_alt(env->N, grid, block, dyn, s, q, fear_alt);
     }));
     HIP_TRY(rec);
     return GW_OK;

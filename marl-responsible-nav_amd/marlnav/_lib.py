@@ -28,7 +28,8 @@ HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_op
                os.path.join(CSRC, "maddpg_dense.hip"), os.path.join(CSRC, "maddpg_desc.hip"),
                os.path.join(CSRC, "patch_ops.hip"), os.path.join(CSRC, "replay_patch.hip"),
                os.path.join(CSRC, "fear_full.hip"), os.path.join(CSRC, "fear_preview.hip"),
-               os.path.join(CSRC, "fear_shield_joint.hip"), os.path.join(CSRC, "resp_map.hip")]
+               os.path.join(CSRC, "fear_shield_joint.hip"), os.path.join(CSRC, "resp_map.hip"),
+               os.path.join(CSRC, "fear_cf.hip"), os.path.join(CSRC, "fear_matrix.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
@@ -39,7 +40,7 @@ SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.jo
                                    os.path.join(CSRC, "draw_action.h"), os.path.join(CSRC, "fear_shield.h"),
                                    os.path.join(CSRC, "np_sum.h"), os.path.join(CSRC, "mlp_rows.h"),
                                    os.path.join(CSRC, "grad_core.h"), os.path.join(CSRC, "desc_rows.h"),
-                                   os.path.join(CSRC, "resp_map.h")]
+                                   os.path.join(CSRC, "resp_map.h"), os.path.join(CSRC, "fear_alt_core.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -51,6 +51,15 @@ def test_entry_point_is_declared_and_exported():
     assert os.path.join(_lib.CSRC, "fear_shield_joint.hip") in _lib.HIP_SOURCES
     src = open(os.path.join(_lib.CSRC, "gridenv.hip")).read()
     assert "fear_shield_joint_kernel" not in src and '#include "np_sum.h"' in src
+    # the table kernel, FeAL and the snapshot matrix live in their own files; the task body exists once
+    for name in ("fear_cf.hip", "fear_matrix.hip"):
+        assert os.path.join(_lib.CSRC, name) in _lib.HIP_SOURCES
+    assert not re.search(r"__global__[^;{]*\b(fear_alt_kernel|feal_kernel|fear_matrix_kernel)\(", src)
+    assert all(k + "<" not in src for k in ("fear_alt_kernel", "feal_kernel", "fear_matrix_kernel"))
+    assert '#include "draw_action.h"' in src
+    callers = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith((".hip", ".h"))
+                     and "fear_alt::decode(" in open(os.path.join(_lib.CSRC, f)).read())
+    assert callers == ["fear_alt_core.h"]
     for doc in (os.path.join(_lib.INCLUDE, "rollout_ops.h"), os.path.join(_lib.CSRC, "fear_shield.h")):
         assert "gw_fear_shield_joint" in open(doc).read()
 

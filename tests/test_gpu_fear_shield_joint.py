@@ -7,7 +7,8 @@
    aliasing rl_actions.  Every factor's every value occurs in each scenario's combination list.
 2. Equals the CPU reference (tests/_fear_shield_joint_ref.py) on the seeded clustered cases, whose floors
    tests/test_fear_shield_joint_cpu.py holds.
-3. Through a step on the defer, defer_narrow and merged paths.
+3. Through a step on the defer, defer_narrow and merged paths.  The shield's table with nobody shielded, the
+   preview's and the step's fear_alt are one table (csrc/fear_alt_core.h from both kernels) at N = 2, 5, 8, E = 5.
 4. sweeps = 1, agents = 1 << k equals gw_fear_shield on the same preview table.
 5. It changes nothing: twin env, two calls in a row, beside the unjoined FeAR kernels, FeAR-off env.
 6. Edges: E in {1, 3, 5, 257}; envs that converge after different sweep counts inside one block; an out-of-range
@@ -190,6 +191,35 @@ def test_through_a_step(path, monkeypatch):
         ok = (flags & 4) == 0
         assert bool((r.fear[ok] <= tau).all()) and bool(ok.any()) and bool((~ok).any())
         env.close()
+
+
+# The table code the shield and fear_alt_kernel share (csrc/fear_alt_core.h), from both kernels on one state, at
+# the smallest shapes where it branches: N = 2 on H*W = 4; N = K = 5, the first agent count with pair lists;
+# N = K = 8, the largest sets.  E = 5: one full block and a block whose last three waves are past the env range.
+# Seeds: clustered spawns (tests/_fear_shield_joint_ref.clustered) whose tables are not all zero.
+CORE_CASES = {"2x2_n2_k2": 921, "5x8_n5_k5": 922, "64x64_n8_k8": 923}
+
+
+@pytest.mark.parametrize("sid", sorted(CORE_CASES))
+def test_shield_preview_and_step_give_one_table(sid):
+    sc = R.scenario(sid)
+    E = 5
+    spawn, rl, scripted, _, _ = R.clustered(sc, CORE_CASES[sid], E)
+    env = VecGridEnv(sc, num_envs=E, fear=True, fear_weight=-5.0, seed=3, max_steps=1000, debug=True, fear_alt=True)
+    dev = env.device
+    env.reset(spawn=torch.as_tensor(spawn.copy()))
+    rl_d, sa_d = _dev(rl, dev), _dev(scripted, dev)
+    buf = _poison(env)
+    out, _, table = env.fear_shield_joint(rl_d, sa_d, agents=0, sweeps=1, **buf)  # the shield's run(all) and row
+    preview = env.fear_preview(rl_d, sa_d).clone()                               # fear_alt_kernel on the same record
+    env.out["fear_alt"].fill_(float("nan"))
+    r = env.step(out, sa_d)
+    torch.cuda.synchronize()
+    assert torch.equal(out, rl_d)
+    assert not bool(torch.isnan(table).any()) and bool((table != 0).any())
+    assert torch.equal(table, preview), sid
+    assert torch.equal(table, r.fear_alt), sid
+    env.close()
 
 
 # ---- 4. one agent, one sweep -----------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 // with a host compiler and the sanitizers and run it,
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -I marl-responsible-nav_amd/csrc tools/fear_alt_tasks_check.cpp -o /tmp/fear_alt_tasks_check
-// It walks every (N, K, close count, task) the kernel can meet, and the out-of-range inputs the
+// It walks every (N, K, close count, task) the kernel can meet, the actor search of a run over a subset
+// of the actors (actor_of, csrc/fear_alt_core.h's callers), and the out-of-range inputs the
 // kernel clamps, and indexes real arrays of the kernel's LDS sizes so that a bad index is a
 // sanitizer error, not a silent pass.  tests/test_fear_alt_cpu.py runs it when a compiler is there.
 #include <cstdint>
@@ -19,6 +20,64 @@
             std::exit(1);                                                             \
         }                                                                             \
     } while (0)
+
+// actor_of against the straightforward walk: the actors of `sel` in ascending order, each with its tasks in order.
+// Actors outside sel keep their counts (the kernels' plan holds every actor's), actors from K on have none.
+template <int N>
+long check_actor_of(uint32_t sel, const int (&tcount)[N]) {
+    using namespace fear_alt;
+    int ti = 0;
+    for (int k = 0; k < N; ++k) {
+        if (!((sel >> k) & 1u)) continue;
+        for (int r = 0; r < tcount[k]; ++r, ++ti) {
+            const Actor t = actor_of<N>(sel, tcount, ti);
+            CHECK(t.k == k && t.r == r);
+        }
+    }
+    // past the total: an actor inside the array, a task number decode clamps
+    const Actor past = actor_of<N>(sel, tcount, ti);
+    CHECK(past.k >= 0 && past.k < N && past.r >= 0);
+    return ti;
+}
+
+// Every K <= N and non-zero sel below 1 << K.  Close counts: every combination over the selected actors where
+// that is at most N^FULL vectors (all of them for N <= 4); beyond, the search being one comparison and one
+// subtraction per actor position, every count 1..N at every selected position over a mixed background, and
+// every count at all positions at once.  Every ti below the total each time.
+template <int N>
+long check_actor_of_all() {
+    using namespace fear_alt;
+    constexpr int FULL = N <= 4 ? N : 3;
+    long walked = 0;
+    for (int K = 1; K <= N; ++K) {
+        for (uint32_t sel = 1; sel < (1u << K); ++sel) {
+            int tcount[N];
+            auto fill = [&](auto count_of) {  // count_of(q): close count of actor q < K
+                for (int q = 0; q < N; ++q) tcount[q] = q < K ? per_actor(count_of(q)) : 0;
+                walked += check_actor_of<N>(sel, tcount);
+            };
+            const int m = __builtin_popcount(sel);
+            if (m <= FULL) {
+                int vectors = 1;
+                for (int i = 0; i < m; ++i) vectors *= N;
+                for (int v = 0; v < vectors; ++v)
+                    fill([&](int q) {
+                        if (!((sel >> q) & 1u)) return 1 + (q + v) % N;  // not selected: must not matter
+                        int digit = v;
+                        for (int i = __builtin_popcount(sel & ((1u << q) - 1u)); i > 0; --i) digit /= N;
+                        return 1 + digit % N;
+                    });
+            } else {
+                for (int c = 1; c <= N; ++c) {
+                    fill([&](int) { return c; });
+                    for (int at = 0; at < K; ++at)
+                        if ((sel >> at) & 1u) fill([&](int q) { return q == at ? c : 1 + (q * 5 + 3) % N; });
+                }
+            }
+        }
+    }
+    return walked;
+}
 
 int main() {
     using namespace fear_alt;
@@ -86,6 +145,9 @@ int main() {
         }
         CHECK(m == (0x1FFu & ~(1u << own)));
     }
-    std::printf("fear_alt task arithmetic ok: %ld tasks walked\n", tasks);
+    const long searched = check_actor_of_all<2>() + check_actor_of_all<3>() + check_actor_of_all<4>() +
+                          check_actor_of_all<5>() + check_actor_of_all<6>() + check_actor_of_all<7>() +
+                          check_actor_of_all<8>();
+    std::printf("fear_alt task arithmetic ok: %ld tasks walked, %ld actor searches\n", tasks, searched);
     return 0;
 }
