@@ -190,6 +190,35 @@ gw_status gw_feal_accum(const double *feal, const uint8_t *active, int64_t E, in
 gw_status gw_resp_map_accum(const uint16_t *resp_valid, const int32_t *cells, const uint8_t *active,
                             uint64_t *counts, uint64_t *visits, int32_t E, int32_t N, int32_t HW, void *stream);
 
+/* Responsibility footprints: the same sets binned by the ACTOR'S ACTION and the affected agent's OFFSET from
+ * the actor, an egocentric map of how far and in which direction an action restricts others.
+ * resp_valid, cells, active: as gw_resp_map_accum takes them; actions [E][N] i32 the step's joint action (the
+ * step's `actions` output; 4-byte aligned); crash_bits [E] u8 or NULL (the step's `crash_bits` output: bit j =
+ * agent j crashed in the step); R in 1..15 the radius of the near window; O = (2R + 1)^2 + 1;
+ * counts [2][9][O][10][10] u64 and visits [9] u64 (may be NULL), both ADDED to (8-byte aligned; the caller
+ * zeroes them once).  For every env e (active[e] != 0, or all if active == NULL) and ordered pair i != j, with
+ * vm, va the popcounts as above, a = actions[e][i] (outside 0..8: 0, as the step reads it),
+ * dr = cells[j][e] / W - cells[i][e] / W, dc = cells[j][e] % W - cells[i][e] % W and
+ * o = (dr + R) (2R + 1) + (dc + R) if |dr| <= R and |dc| <= R, else the far bin (2R + 1)^2:
+ *   counts[0][a][o][vm][va] += 1;
+ *   counts[1][a][o][vm][va] += 1    if crash_bits != NULL and bit j of crash_bits[e] is set
+ *                                   (crash_bits == NULL: plane 1 is not touched);
+ *   visits[a] += 1                  once per (e, i).
+ * The sum of the Resp that action a caused at offset o is sum_vm sum_va counts[0][a][o][vm][va] * T[vm][va],
+ * formed on the host in that fixed order (marlnav.resp_footprint_from_counts).  The device only counts, so the
+ * result is the same bit for bit eager, replayed and all-reduced, as the maps' is.  Every cell is clamped to
+ * [0, H W) and every popcount to [0, 9] before it indexes anything (csrc/resp_footprint.h, the same text the
+ * CPU check runs).  One launch of 256-thread blocks, one thread per (i, j, e) with e fastest; the lanes of a
+ * wave that hold the same bin are merged into one 64-bit global atomic add without return of their number; no
+ * LDS, no allocation, no host sync: graph-capturable.  Call it after the FeAR fence, and before gw_eval_accum
+ * in an evaluation step.  It has no env handle and so no gw_profile_spans kind.
+ * GW_ERR_ARG (with a gw_last_error message): NULL resp_valid, cells, actions or counts; N outside 2..8;
+ * E <= 0, H <= 0 or W <= 0 (or H W beyond int32); R outside 1..15; a misaligned pointer. */
+gw_status gw_resp_footprint_accum(const uint16_t *resp_valid, const int32_t *cells, const int32_t *actions,
+                                  const uint8_t *crash_bits, const uint8_t *active, uint64_t *counts,
+                                  uint64_t *visits, int32_t E, int32_t N, int32_t H, int32_t W, int32_t R,
+                                  void *stream);
+
 /* The responsibility shield: replace an RL action whose previewed FeAR exceeds tau, before the world moves.
  * fear_alt [E][K][9] f64 (gw_fear_preview's table for the proposed joint action), actions_in / actions_out
  * [E][K] i32 (may be the same buffer), mask [E][K] u16 9-bit action masks (NULL: all nine), probs

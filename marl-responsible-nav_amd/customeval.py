@@ -35,6 +35,12 @@ def main(argv=None):
                     help="also print two H x W responsibility maps: the mean Resp an agent standing on a cell "
                          "caused to the others per visit, and the mean Resp it received there; runs the env with "
                          "FeAR on.  With a file name, save counts, visits and the maps there (numpy .npz)")
+    ap.add_argument("--resp-footprint", nargs="?", type=int, const=5, default=None, metavar="R",
+                    help="also print the responsibility footprint: per action of the actor, the mean Resp it caused "
+                         "per actor-step to an agent standing at each offset (dr, dc) within radius R (default 5), "
+                         "and the share of the total absolute Resp that falls beyond R; runs the env with FeAR on")
+    ap.add_argument("--resp-footprint-file", default=None, metavar="FILE.npz",
+                    help="with --resp-footprint: save counts, visits and the footprint there (numpy .npz)")
     ap.add_argument("--shield", type=float, default=None, metavar="TAU",
                     help="responsibility shield: before every step, replace an RL action whose previewed FeAR "
                          "exceeds TAU by an allowed one (the most probable under the actor); also prints how many "
@@ -65,9 +71,10 @@ def main(argv=None):
         actors = m.actors
     resp_map = args.resp_map is not None
     r = evaluate(actors, sc, episodes=args.episodes, max_steps=args.train_steps,
-                 fear=args.feal or args.resp_full or resp_map,
+                 fear=args.feal or args.resp_full or resp_map or args.resp_footprint is not None,
                  seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield,
-                 shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps, resp_map=resp_map)
+                 shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps, resp_map=resp_map,
+                 resp_footprint=args.resp_footprint)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
@@ -96,6 +103,27 @@ def main(argv=None):
             np.savez(args.resp_map, counts=r["resp_map_counts"].numpy(), visits=visits, resp_map=maps,
                      mean_caused=mean[0], mean_received=mean[1])
             print(f"Responsibility maps saved to {args.resp_map}")
+    if args.resp_footprint is not None:
+        import numpy as np
+        from marlnav.resp_footprint import resp_footprint_from_counts
+        R = args.resp_footprint
+        counts, visits = r["resp_footprint_counts"], r["resp_footprint_visits"].numpy()
+        fp, _, (near, far) = resp_footprint_from_counts(counts)
+        near, far = near[0].numpy(), far[0].numpy()
+        for a in range(9):
+            print(f"Action {a}: {int(visits[a])} actor-steps; mean Resp caused per actor-step at offset (dr, dc), "
+                  f"|dr|, |dc| <= {R}; beyond: {far[a] / max(int(visits[a]), 1):.6f}")
+            for y in range(2 * R + 1):
+                print("  " + " ".join(f"{v:7.4f}" for v in (near[a, y] / max(int(visits[a]), 1)).tolist()))
+        # the absolute Resp per bin: |T[vm][va]| weights, in the fixed order of the footprint itself
+        from marlnav.resp_map import resp_table
+        mag = resp_footprint_from_counts(counts, np.abs(resp_table()))[0][0].numpy()
+        total = float(mag.sum())
+        print(f"Far share of the absolute Resp (beyond radius {R}): "
+              f"{(float(mag[:, -1].sum()) / total if total else 0.0):.6f} of {total:.6f}")
+        if args.resp_footprint_file:
+            np.savez(args.resp_footprint_file, counts=counts.numpy(), visits=visits, footprint=fp.numpy(), radius=R)
+            print(f"Responsibility footprint saved to {args.resp_footprint_file}")
 
 
 if __name__ == "__main__":

@@ -29,7 +29,8 @@ HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_op
                os.path.join(CSRC, "patch_ops.hip"), os.path.join(CSRC, "replay_patch.hip"),
                os.path.join(CSRC, "fear_full.hip"), os.path.join(CSRC, "fear_preview.hip"),
                os.path.join(CSRC, "fear_shield_joint.hip"), os.path.join(CSRC, "resp_map.hip"),
-               os.path.join(CSRC, "fear_cf.hip"), os.path.join(CSRC, "fear_matrix.hip")]
+               os.path.join(CSRC, "fear_cf.hip"), os.path.join(CSRC, "fear_matrix.hip"),
+               os.path.join(CSRC, "resp_footprint.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
@@ -40,7 +41,8 @@ SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.jo
                                    os.path.join(CSRC, "draw_action.h"), os.path.join(CSRC, "fear_shield.h"),
                                    os.path.join(CSRC, "np_sum.h"), os.path.join(CSRC, "mlp_rows.h"),
                                    os.path.join(CSRC, "grad_core.h"), os.path.join(CSRC, "desc_rows.h"),
-                                   os.path.join(CSRC, "resp_map.h"), os.path.join(CSRC, "fear_alt_core.h")]
+                                   os.path.join(CSRC, "resp_map.h"), os.path.join(CSRC, "fear_alt_core.h"),
+                                   os.path.join(CSRC, "resp_footprint.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -203,7 +205,7 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_set_fear_alt", "gw_fear_regret_accum",
            "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts", "gw_set_obs_ride", "gw_obs_ride_count",
            "gw_set_feal", "gw_feal_accum", "gw_set_fear_full", "gw_fear_preview", "gw_fear_shield",
-           "gw_fear_shield_joint", "gw_resp_map_accum"]
+           "gw_fear_shield_joint", "gw_resp_map_accum", "gw_resp_footprint_accum"]
 
 
 class GwObsSource(C.Structure):
@@ -369,6 +371,8 @@ def _declare(L):
     L.gw_fear_shield_joint.restype = C.c_int
     L.gw_resp_map_accum.argtypes = [p, p, p, p, p, C.c_int32, C.c_int32, C.c_int32, p]
     L.gw_resp_map_accum.restype = C.c_int
+    L.gw_resp_footprint_accum.argtypes = [p] * 7 + [C.c_int32] * 5 + [p]
+    L.gw_resp_footprint_accum.restype = C.c_int
     L.gw_affine_relu_fwd.argtypes = [p, p, p, p, C.c_int32, C.c_int64, C.c_int32, p]
     L.gw_affine_relu_fwd.restype = C.c_int
     L.gw_affine_relu_bwd.argtypes = [p] * 7 + [C.c_int32, C.c_int64, C.c_int32, p]

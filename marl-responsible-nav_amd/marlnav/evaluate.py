@@ -31,7 +31,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
              fear: bool = False, seed: int = 42, record_actions: bool = False, fused: bool | None = None,
              variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False,
              feal: bool = False, resp_full: bool = False, shield: float | None = None,
-             shield_mode: str = "unilateral", shield_sweeps: int = 2, resp_map: bool = False) -> dict:
+             shield_mode: str = "unilateral", shield_sweeps: int = 2, resp_map: bool = False,
+             resp_footprint: int | None = None) -> dict:
     """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
     matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
     restricted agent j) summed over the episodes still running and divided by "steps".
@@ -51,6 +52,12 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
     1: at the cell of the agent that received it), "resp_map_counts" (int64 [2, H*W, 10, 10], the exact counts
     per cell and valid-action counts (vm, va) the map is formed from) and "resp_map_visits" (int64 [H*W],
     agent-steps per cell): ``resp_map.reshape(2, -1) / resp_map_visits`` is the mean per visit.
+    resp_footprint (a radius R in 1..15, with ``fear=True``): the result also carries the responsibility
+    footprint of the episodes still running (gw_resp_footprint_accum with the ``active`` mask, on the cells
+    copied before each step, the step's joint action and its crash bits): "resp_footprint" [2, 9, O] f64 (per
+    action of the actor and offset of the affected agent from it, O = (2R + 1)^2 + 1 with the far bin last, the
+    Resp summed; plane 1: the affected agents that crashed in the step), "resp_footprint_counts" (int64
+    [2, 9, O, 10, 10]) and "resp_footprint_visits" (int64 [9], actor-steps per action).
     shield (a float tau; None: off): the responsibility shield at inference time.  Every step runs actor,
     ``env.fear_preview`` of the proposed actions, ``env.fear_shield`` (the env's action mask, the actor's
     probabilities, every RL agent shielded), then ``env.step`` with the shielded actions; works with
@@ -73,13 +80,18 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         raise ValueError("evaluate(resp_full=True) needs fear=True")
     if resp_map and not fear:
         raise ValueError("evaluate(resp_map=True) needs fear=True")
+    footprint = resp_footprint is not None
+    if footprint and not fear:
+        raise ValueError("evaluate(resp_footprint=R) needs fear=True")
+    if footprint and not 1 <= int(resp_footprint) <= 15:
+        raise ValueError("evaluate(resp_footprint=R): R in 1..15")
     sc = builtin(scenario) if isinstance(scenario, str) else scenario
     if fused is None:
         fused = actors.fusable(SimpleNamespace(K=sc.K, H=sc.H, W=sc.W))
     # the fused actor reads the obs descriptors: no dense obs is written at all
     env = VecGridEnv(sc, num_envs=episodes, fear=fear, max_steps=max_steps, auto_reset=False, seed=seed,
                      obs=not fused, variant=variant, fear_rows=resp_matrix, fear_alt=fear_regret, feal=feal,
-                     fear_full=resp_full or resp_map)
+                     fear_full=resp_full or resp_map or footprint, debug=footprint)
     try:
         obs, mask = env.reset()
         dev = env.device
@@ -98,7 +110,10 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         hw = env.H * env.W
         map_counts = torch.zeros((2, hw, 10, 10), dtype=torch.int64, device=dev) if resp_map else None
         map_visits = torch.zeros(hw, dtype=torch.int64, device=dev) if resp_map else None
-        map_cells = torch.empty((env.N, episodes), dtype=torch.int32, device=dev) if resp_map else None
+        map_cells = torch.empty((env.N, episodes), dtype=torch.int32, device=dev) if resp_map or footprint else None
+        if footprint:
+            fp_counts = torch.zeros((2, 9, (2 * int(resp_footprint) + 1) ** 2 + 1, 10, 10), dtype=torch.int64, device=dev)
+            fp_visits = torch.zeros(9, dtype=torch.int64, device=dev)
         table = torch.empty((episodes, env.K, 9), dtype=torch.float64, device=dev) if shield is not None else None
         # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
         shield_cnt = torch.zeros((4 if joint_mode else 2, env.K), dtype=torch.int64, device=dev)
@@ -124,11 +139,14 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
                 shield_cnt[1] += ((flags >> 1) * on).sum(0)
             if record_actions:
                 recorded.append(actions.clone())
-            if resp_map:  # the step's pre-move cells
+            if map_cells is not None:  # the step's pre-move cells
                 env.copy_pos(map_cells)
             r = env.step(actions)
             if resp_map:  # the active envs' sets binned by cell, likewise before the done ones are retired
                 env.resp_map_accum(r.resp_valid, map_cells, map_counts, map_visits, active=active)
+            if footprint:  # and by the actor's action and the affected agent's offset, likewise
+                env.resp_footprint_accum(r.resp_valid, map_cells, r.actions, fp_counts, fp_visits,
+                                         crash_bits=r.crash_bits, active=active, radius=int(resp_footprint))
             if resp_matrix:  # the active envs' Resp rows, before gw_eval_accum retires the done ones
                 _lib.check(lib.gw_fear_row_accum(r.fear_row.data_ptr(), active.data_ptr(), episodes, env.K, env.N,
                                                  resp.data_ptr(), resp_calls.data_ptr(),
@@ -172,6 +190,10 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             from .resp_map import resp_map_from_counts
             out["resp_map_counts"], out["resp_map_visits"] = map_counts.cpu(), map_visits.cpu()
             out["resp_map"] = resp_map_from_counts(out["resp_map_counts"])[0].reshape(2, env.H, env.W)
+        if footprint:
+            from .resp_footprint import resp_footprint_from_counts
+            out["resp_footprint_counts"], out["resp_footprint_visits"] = fp_counts.cpu(), fp_visits.cpu()
+            out["resp_footprint"] = resp_footprint_from_counts(out["resp_footprint_counts"])[0]
         if shield is not None:
             out["shield_replaced"], out["shield_stuck"] = shield_cnt[0].cpu(), shield_cnt[1].cpu()
             if joint_mode:

@@ -213,7 +213,7 @@ class Rollout:
                  patch_async: bool | None = None, desc_ring: bool | str = False, resp_matrix: bool = False,
                  fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
                  shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2,
-                 resp_map: bool = False):
+                 resp_map: bool = False, resp_footprint: int | None = None):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -270,6 +270,16 @@ class Rollout:
         (int64 [H*W], agent-steps per cell) and the derived "resp_map" ([2, H, W] f64, the summed Resp per
         cell: ``marlnav.resp_map_from_counts``).  The device keeps integer counts, so the totals are the same
         bit for bit eager or replayed, and several ranks all-reduce the integers.
+        resp_footprint (a radius R in 1..15; None: off; an env built with ``fear_full=True`` and ``debug=True``,
+        whose steps report ``actions`` and ``crash_bits``): how far, and in which direction, an action restricts
+        others.  The cells are copied before every step as for ``resp_map`` and the step's sets are binned by
+        the actor's action and the affected agent's offset from it where ``resp_map`` is folded
+        (gw_resp_footprint_accum, one launch per step, under the same rule inside ``capture`` graphs), the
+        affected agents that crashed in the step into a second plane; ``totals()`` then carries
+        "resp_footprint_counts" (int64 [2, 9, O, 10, 10], O = (2R + 1)^2 + 1: the near offsets row-major, then
+        the far bin), "resp_footprint_visits" (int64 [9], actor-steps per action) and the derived
+        "resp_footprint" ([2, 9, O] f64, the summed Resp per action and offset:
+        ``marlnav.resp_footprint_from_counts``).  Integer counts, all-reduced as integers.
         shield (a float tau; None: off, no extra launch): the responsibility shield.  Every step runs actor,
         then ``env.fear_preview`` of the proposed actions, then ``env.fear_shield`` (the env's action mask, the
         actor's probabilities, every RL agent shielded), then ``env.step`` with the shielded actions.  The ring
@@ -383,6 +393,21 @@ class Rollout:
             self._map_counts = torch.zeros((2, hw, 10, 10), dtype=torch.int64, device=env.device)
             self._map_visits = torch.zeros(hw, dtype=torch.int64, device=env.device)
             self._map_cells = torch.empty((env.N, env.E), dtype=torch.int32, device=env.device)
+        self._fp_counts = self._fp_visits = None
+        self._fp_radius = None if resp_footprint is None else int(resp_footprint)
+        if self._fp_radius is not None:
+            if env.out.get("resp_valid") is None:
+                raise ValueError("Rollout(resp_footprint=R) needs VecGridEnv(fear_full=True)")
+            if env.out.get("actions") is None or env.out.get("crash_bits") is None:
+                raise ValueError("Rollout(resp_footprint=R) needs VecGridEnv(debug=True) (the step's actions and "
+                                 "crash_bits)")
+            if not 1 <= self._fp_radius <= 15:
+                raise ValueError("Rollout(resp_footprint=R): R in 1..15")
+            n_off = (2 * self._fp_radius + 1) ** 2 + 1
+            self._fp_counts = torch.zeros((2, 9, n_off, 10, 10), dtype=torch.int64, device=env.device)
+            self._fp_visits = torch.zeros(9, dtype=torch.int64, device=env.device)
+            if self._map_cells is None:
+                self._map_cells = torch.empty((env.N, env.E), dtype=torch.int32, device=env.device)
         self._full = self._full_steps = None
         if resp_full:
             if env.out.get("resp_full") is None:
@@ -473,6 +498,10 @@ class Rollout:
                        "gw_fear_row_accum")
         if self._map_counts is not None:  # the step's sets (FeAR-owned) binned by the cells copied before it
             self.env.resp_map_accum(self.env.out["resp_valid"], self._map_cells, self._map_counts, self._map_visits)
+        if self._fp_counts is not None:  # the same sets by the actor's action and the affected agent's offset
+            out = self.env.out
+            self.env.resp_footprint_accum(out["resp_valid"], self._map_cells, out["actions"], self._fp_counts,
+                                          self._fp_visits, crash_bits=out["crash_bits"], radius=self._fp_radius)
         if self.gather is not None:
             self.gather.push()  # the step wrote ep_return / done into the gather's send buffer
         if self._acc is not None:
@@ -784,6 +813,9 @@ class Rollout:
         With ``resp_map``: "resp_map_counts" (int64 [2, H*W, 10, 10] CPU tensor, summed over the ranks in an
         integer all-reduce of its own), "resp_map_visits" (int64 [H*W]) and "resp_map" ([2, H, W] f64:
         ``marlnav.resp_map_from_counts`` of the counts; plane 0 the Resp caused at a cell, plane 1 received).
+        With ``resp_footprint``: "resp_footprint_counts" (int64 [2, 9, O, 10, 10] CPU tensor, all-reduced as
+        integers), "resp_footprint_visits" (int64 [9]) and "resp_footprint" ([2, 9, O] f64:
+        ``marlnav.resp_footprint_from_counts`` of the counts; plane 1 the affected agents that crashed).
         With ``shield``: "shield_replaced" [K] and "shield_stuck" [K] (int64 CPU tensors): the agent-steps whose
         action the shield replaced (flag bit 0) / that had no allowed action (flag bit 1).  With
         ``shield_mode="joint"`` also "shield_over" [K] (agent-steps whose applied action's FeAR exceeds tau, flag
@@ -791,7 +823,7 @@ class Rollout:
         With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
         the responsibility total): every rank calls it."""
         if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
-                and self._full is None and self._shield_cnt is None):
+                and self._full is None and self._shield_cnt is None and self._fp_counts is None):
             return {}
         if self._shield_cnt is not None:  # its own small all-reduce: exact integer counts
             cnt = self._shield_cnt.clone()
@@ -801,7 +833,7 @@ class Rollout:
             if self.shield_mode == "joint":
                 shield["shield_over"], shield["shield_unconverged"] = cnt[2].cpu(), int(cnt[3, 0])
             if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
-                    and self._full is None):
+                    and self._full is None and self._fp_counts is None):
                 self._flush()
                 return shield
         else:
@@ -818,8 +850,10 @@ class Rollout:
             parts.append(self._feal_cnt[1:2].to(torch.float64))
         if self._full is not None:
             parts.append(self._full.reshape(-1))
+        if not parts:  # only the footprint's integer counts below
+            parts.append(torch.zeros(0, dtype=torch.float64, device=self.env.device))
         local = torch.cat(parts) if len(parts) > 1 else parts[0].clone()  # (the all-reduce is in place)
-        if self.distributed:
+        if self.distributed and local.numel():
             dist.all_reduce(local, group=self.group)
         out = dict(zip(_lib.STATS_NAMES, local[:nst].cpu().tolist()))
         if self._resp is not None:
@@ -849,6 +883,14 @@ class Rollout:
             from .resp_map import resp_map_from_counts
             out["resp_map_counts"], out["resp_map_visits"] = cnt.cpu(), vis.cpu()
             out["resp_map"] = resp_map_from_counts(out["resp_map_counts"])[0].reshape(2, self.env.H, self.env.W)
+        if self._fp_counts is not None:  # likewise
+            cnt, vis = self._fp_counts.clone(), self._fp_visits.clone()
+            if self.distributed:
+                dist.all_reduce(cnt, group=self.group)
+                dist.all_reduce(vis, group=self.group)
+            from .resp_footprint import resp_footprint_from_counts
+            out["resp_footprint_counts"], out["resp_footprint_visits"] = cnt.cpu(), vis.cpu()
+            out["resp_footprint"] = resp_footprint_from_counts(out["resp_footprint_counts"])[0]
         out.update(shield)
         return out
 

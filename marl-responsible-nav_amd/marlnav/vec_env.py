@@ -581,6 +581,41 @@ class VecGridEnv:
             _lib.check(self.lib.gw_resp_map_accum(_ptr(resp_valid), _ptr(cells), _ptr(active), _ptr(counts),
                                                   _ptr(visits), E, N, HW, self._stream()), "gw_resp_map_accum")
 
+    def resp_footprint_accum(self, resp_valid: torch.Tensor, cells: torch.Tensor, actions: torch.Tensor,
+                             counts: torch.Tensor, visits: torch.Tensor | None = None,
+                             crash_bits: torch.Tensor | None = None, active: torch.Tensor | None = None,
+                             radius: int = 5):
+        """Bin one step's N x N valid-action sets by the actor's action and the affected agent's offset from the
+        actor (gw_resp_footprint_accum, include/rollout_ops.h): for every env (``active[e] != 0`` if a mask is
+        given) and ordered pair i != j, ``counts[0, actions[e, i], o, vm, va] += 1`` with o the bin of the offset
+        (dr, dc) of ``cells[j, e]`` from ``cells[i, e]`` (the far bin beyond ``radius``), the same into
+        ``counts[1]`` if bit j of ``crash_bits[e]`` is set, and ``visits[actions[e, i]] += 1`` once per (e, i).
+        resp_valid: [E, N, N, 2] int16 (StepResult.resp_valid); cells: [N, E] int32 (``copy_pos`` before the
+        step); actions: [E, N] int32 (StepResult.actions, an env created with ``debug=True``); counts:
+        [2, 9, O, 10, 10] int64 with O = (2 radius + 1)^2 + 1 and visits: [9] int64 or None, both added to;
+        crash_bits: [E] uint8 (StepResult.crash_bits) or None (plane 1 untouched); active: [E] uint8 or None;
+        radius: 1..15.  ``marlnav.resp_footprint_from_counts`` turns the counts into the footprint.  Raises on
+        an env created without ``fear_full=True``."""
+        if self.out.get("resp_valid") is None:
+            raise ValueError("resp_footprint_accum needs VecGridEnv(fear_full=True) (the step's resp_valid sets)")
+        R = int(radius)
+        if not 1 <= R <= 15:
+            raise ValueError("resp_footprint_accum(radius=...): 1..15")
+        E, N, O = self.E, self.N, (2 * R + 1) ** 2 + 1
+        for t, dt, n, name in ((resp_valid, torch.int16, 2 * E * N * N, "resp_valid"), (cells, torch.int32, N * E, "cells"),
+                               (actions, torch.int32, E * N, "actions"), (counts, torch.int64, 2 * 9 * O * 100, "counts"),
+                               (visits, torch.int64, 9, "visits"), (crash_bits, torch.uint8, E, "crash_bits"),
+                               (active, torch.uint8, E, "active")):
+            if t is None and name in ("visits", "crash_bits", "active"):
+                continue
+            if t is None or t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"resp_footprint_accum({name}=...): need a contiguous {dt} tensor of {n} elements on "
+                                 f"{self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_resp_footprint_accum(_ptr(resp_valid), _ptr(cells), _ptr(actions), _ptr(crash_bits),
+                                                        _ptr(active), _ptr(counts), _ptr(visits), E, N, self.H, self.W,
+                                                        R, self._stream()), "gw_resp_footprint_accum")
+
     def fear_preview(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
                      out: torch.Tensor | None = None, actions: torch.Tensor | None = None,
                      mdr: torch.Tensor | None = None) -> torch.Tensor:
