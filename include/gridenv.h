@@ -164,7 +164,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * GW_SPAN_FEAL the per-agent FeAL kernel (feal_kernel, gw_set_feal),
  * GW_SPAN_FEAR_FULL the N x N responsibility matrix's kernel (fear_full_kernel, gw_set_fear_full),
  * GW_SPAN_FEAR_PREVIEW the two launches of gw_fear_preview (preview_rec_kernel, fear_alt_kernel),
- * GW_SPAN_FEAR_SHIELD the two launches of gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel).
+ * GW_SPAN_FEAR_SHIELD the two launches of gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel),
+ * GW_SPAN_STEP_PREVIEW the two launches of gw_step_preview (preview_rec_kernel, step_preview_kernel).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -173,7 +174,8 @@ enum {
     GW_SPAN_STEP = 0, GW_SPAN_OBS = 1, GW_SPAN_FEAR = 2, GW_SPAN_ACT = 3, GW_SPAN_CNN_L1 = 4,
     GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8,
     GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11, GW_SPAN_FEAR_PREVIEW = 12,
-    GW_SPAN_FEAR_SHIELD = 13 /* the two launches of one gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel) */
+    GW_SPAN_FEAR_SHIELD = 13 /* the two launches of one gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel) */,
+    GW_SPAN_STEP_PREVIEW = 14 /* the two launches of one gw_step_preview (preview_rec_kernel, step_preview_kernel) */
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -478,6 +480,40 @@ gw_status gw_fear_shield_joint(void *env, const int32_t *rl_actions, const int32
                                const uint16_t *mask, const float *probs, double tau, uint32_t agents,
                                int32_t sweeps, int32_t *actions_out, uint8_t *flags, double *fear_alt,
                                int32_t *joint, void *stream);
+
+/* The step outcome preview: crash bits, restricted bits and env reward of the step that
+ * gw_step(env, rl_actions, scripted, ...) WOULD run next, under each of the nine actions of each RL agent,
+ * without moving the world.  For every env e, RL agent k < K and action a in 0..8 one real UpdateGWorld
+ * (custom/grid_world.py:424-563) of the current world: the FULL joint action that gw_step will apply (far agents
+ * move too: not FeAR's close-list variant) with agent k playing a instead, eaters 0..K-1, the apples still present.
+ *   outcome [E][K][9] u16 (required): bits 0-7 that update's crash bits of all N agents (gw_step_out.crash_bits),
+ *     bits 8-15 its restricted bits (restr_bits);
+ *   reward_alt [E][K][9] f64 or NULL: the env reward gw_step_out.reward[e][k] the step would pay agent k
+ *     (ma_customenv.py:258-302; variant 1: customenv.py:127-160): the own apple once, the all-eaten +20, -10 on
+ *     a crash, +1 / +0.1 for moving closer, from the env's present apples and prev_dist, bit for bit.  It does
+ *     not depend on FeAR;
+ *   crash9 [E][K] u16 or NULL: bit a set when agent k ITSELF crashes under a (bit k of outcome[e][k][a]);
+ *   safe_mask [E][K] u16 or NULL: m & ~crash9 with m = mask[e][k] (mask [E][K] 9-bit action masks; NULL: 0x1FF);
+ *     if that is empty, m unchanged (nothing avoids the crash).  The rule is csrc/step_preview.h's.  Passed to
+ *     gw_fear_shield (include/rollout_ops.h) in the action mask's place it makes the shield crash-aware; with
+ *     a zero table and tau = 0 only crashing proposals are replaced, by the most probable safe action;
+ *   actions [E][N] i32 or NULL: the joint action that step will apply (gw_step_out.actions).
+ * rl_actions / scripted as gw_fear_preview's: NULL draws with the step's own Philox counters.  So
+ * outcome[e][k][actions[e][k]] == crash_bits[e] | restr_bits[e] << 8 and reward_alt[e][k][actions[e][k]] ==
+ * reward[e][k] of that gw_step, for every k.
+ * The preview is UNILATERAL, as gw_fear_shield's rows are: each entry assumes that the other agents play their
+ * proposed actions.  An agent moved to a safe action does not crash in the step only in envs where every other
+ * agent's action was kept.
+ * Conventions of gw_fear_preview: works on cfg.fear == 0 envs; changes no env state, step output, pipeline state
+ * or obs-destination table; keeps a record buffer of its own, allocated by the first call (a first call while
+ * `stream` captures returns GW_ERR_STATE, later calls can be captured); no host synchronisation; GW_ERR_STATE
+ * before the first gw_reset; GW_ERR_ARG on a null env or a null outcome.
+ * Cost: two launches on `stream` (preview_rec_kernel, then step_preview_kernel: one wave per env, the K x 9
+ * tasks (k, a) dealt to its lanes, one register-resident world update per lane and turn; K = 8: 72 tasks, two
+ * turns), one GW_SPAN_STEP_PREVIEW span while profiling; gw_count_sims counts the 9 K world updates per env. */
+gw_status gw_step_preview(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                          uint16_t *outcome, double *reward_alt, uint16_t *crash9, uint16_t *safe_mask,
+                          int32_t *actions, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // cf_env.h -- internal: the device code that gridenv.hip shares with the translation units of the
 // counterfactual FeAR kernels (fear_cf.hip, fear_full.hip, fear_preview.hip, fear_shield_joint.hip,
-// fear_matrix.hip): the launch parameters, one world update in registers (World, simulate, cf_valid), the
+// fear_matrix.hip) and of the step outcome preview (step_preview.hip): the launch parameters, one world update in registers (World, simulate, cf_valid), the
 // step's FearRec, the cell table's bit layout, lds_fill, the CfEnv scaffold and those files' launchers, which
 // gridenv.hip calls.  gridenv.hip includes it where this code used to stand, so its own kernels compile as before.
 #pragma once
@@ -523,6 +523,21 @@ hipError_t launch_fear_full(int N, dim3 grid, dim3 block, size_t dyn, hipStream_
 // the record of the step the next gw_step will run into p.fwork, its joint action and MdRs into actions / mdr
 // ([E][N] or null)
 hipError_t launch_preview_rec(int N, hipStream_t s, const Params &p, int32_t *actions, int32_t *mdr);
+
+// gw_step_preview's outputs beside the env's (include/gridenv.h): mask [E][K] or null, outcome [E][K][9],
+// reward_alt [E][K][9] / crash9 [E][K] / safe_mask [E][K] or null
+struct StepPreviewArgs {
+    const uint16_t *mask;
+    uint16_t *outcome;
+    double *reward_alt;
+    uint16_t *crash9;
+    uint16_t *safe_mask;
+};
+
+// step_preview_kernel<N> (step_preview.hip, gw_step_preview) over p's env range on s, through gwprof::launch,
+// from the record in p.fwork
+hipError_t launch_step_preview(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
+                               const StepPreviewArgs &a);
 
 // gw_fear_shield_joint's arguments beside the env's (include/gridenv.h): mask [E][K] or null, probs [K][E][9] or
 // null, agents / sweeps already checked, actions_out [E][K], flags [E][K] / table [E][K][9] / joint [E][N] or null

@@ -1602,6 +1602,9 @@ struct Env {
     // gw_fear_preview's own record buffer [E][FearRec<N>::R4] (first call): never the step's fwork, which a
     // previous step's fear_alt / FeAL / full-matrix kernels may still be reading on the aux stream
     uint4 *preview_rec = nullptr;
+    // gw_step_preview's own record buffer, likewise (first call): a FeAR preview enqueued on another stream
+    // may be reading preview_rec
+    uint4 *step_preview_rec = nullptr;
     // gw_obs_patch's per-P tables of the map part of every window centre (patch_ops.hip MODE 4)
     std::vector<std::pair<int, float *>> ptbls;
     double *score = nullptr, *fscore = nullptr;
@@ -2932,15 +2935,44 @@ gw_status gw_set_fear_full(void *handle, double *resp_full, uint16_t *resp_valid
     return GW_OK;
 }
 
-// the record buffer gw_fear_preview and gw_fear_shield_joint share, allocated by the first call of either
-static gw_status ensure_preview_rec(Env *env, hipStream_t s, const char *who) {
-    if (env->preview_rec) return GW_OK;
+// the record buffer gw_fear_preview and gw_fear_shield_joint share (env->preview_rec, the default) or
+// gw_step_preview's own, allocated by the first call
+static gw_status ensure_preview_rec(Env *env, hipStream_t s, const char *who, uint4 **rec = nullptr) {
+    if (!rec) rec = &env->preview_rec;
+    if (*rec) return GW_OK;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;  // hipMalloc is not allowed while the stream captures
     HIP_TRY(hipStreamIsCapturing(s, &cs));
     if (cs != hipStreamCaptureStatusNone)
         return fail(GW_ERR_STATE, (std::string(who) + ": the first call allocates the record buffer and cannot run "
                                    "while the stream is capturing; call it once before the capture").c_str());
-    return dalloc(env, &env->preview_rec, (size_t)env->E * (env->N <= 4 ? 1 : 2));
+    return dalloc(env, rec, (size_t)env->E * (env->N <= 4 ? 1 : 2));
+}
+
+gw_status gw_step_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                          uint16_t *outcome, double *reward_alt, uint16_t *crash9, uint16_t *safe_mask,
+                          int32_t *actions, void *stream) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_step_preview: null env");
+    if (!outcome) return fail(GW_ERR_ARG, "gw_step_preview: null outcome");
+    if (!env->initialized) return fail(GW_ERR_STATE, "gw_step_preview before gw_reset");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GW_TRY(ensure_preview_rec(env, s, "gw_step_preview", &env->step_preview_rec));
+    // as gw_fear_preview: the env's state as the next gw_step will read it, nothing of the env written
+    gw::Params p = make_params(env);
+    p.rl = rl_actions;
+    p.scripted = scripted;
+    p.fwork = env->step_preview_rec;
+    const gw::StepPreviewArgs a{mask, outcome, reward_alt, crash9, safe_mask};
+    hipError_t rec = hipSuccess;
+    GW_TRY(launch_cf(env, GW_SPAN_STEP_PREVIEW, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        // the record of the step's joint action (fear_preview.hip), then the K x 9 real world updates on it
+        // (step_preview.hip, its own code object): both launches are the one span
+        rec = gw::launch_preview_rec(env->N, s, q, actions, nullptr);
+        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
+        rec = gw::launch_step_preview(env->N, grid, block, dyn, s, q, a);
+    }));
+    HIP_TRY(rec);
+    return GW_OK;
 }
 
 gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,

@@ -51,7 +51,14 @@ def main(argv=None):
                          "the agent-steps whose applied action still exceeds TAU are printed too")
     ap.add_argument("--shield-sweeps", type=int, default=2, metavar="N",
                     help="joint mode: at most N sweeps over the agents (1..8; a sweep that changes nothing ends them)")
+    ap.add_argument("--shield-crash", action="store_true",
+                    help="crash-aware shield: before every step, preview each RL agent's nine actions with the real "
+                         "world update and keep the shield (or, without --shield, the actor) to actions under which "
+                         "the agent itself does not crash; also prints how many proposals would have crashed and "
+                         "how many of them were replaced.  Unilateral: not with --shield-mode joint")
     args = ap.parse_args(argv)
+    if args.shield_crash and args.shield_mode == "joint":
+        ap.error("--shield-crash is unilateral: not with --shield-mode joint")
 
     from marlnav import scenario as S
     from marlnav.evaluate import evaluate
@@ -74,7 +81,7 @@ def main(argv=None):
                  fear=args.feal or args.resp_full or resp_map or args.resp_footprint is not None,
                  seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield,
                  shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps, resp_map=resp_map,
-                 resp_footprint=args.resp_footprint)
+                 resp_footprint=args.resp_footprint, shield_crash=args.shield_crash)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
@@ -85,6 +92,9 @@ def main(argv=None):
         if args.shield_mode == "joint":
             print(f"Joint shield ({args.shield_sweeps} sweeps): over tau {r['shield_over'].tolist()} agent-steps per RL "
                   f"agent, {r['shield_unconverged']} env-steps unconverged")
+    if args.shield_crash:
+        print(f"Crash shield: {r['shield_crash_proposed'].tolist()} proposals would have crashed the agent, "
+              f"{r['shield_crash_replaced'].tolist()} of them replaced, agent-steps per RL agent")
     if args.feal:
         print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
     if args.resp_full:

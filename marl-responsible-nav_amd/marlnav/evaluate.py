@@ -32,7 +32,7 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
              variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False,
              feal: bool = False, resp_full: bool = False, shield: float | None = None,
              shield_mode: str = "unilateral", shield_sweeps: int = 2, resp_map: bool = False,
-             resp_footprint: int | None = None) -> dict:
+             resp_footprint: int | None = None, shield_crash: bool = False) -> dict:
     """resp_matrix (with ``fear=True``): the result also carries "resp", the [K, N] responsibility
     matrix (f64 CPU tensor): every step's per-pair rows (StepResult.fear_row: how much RL agent k
     restricted agent j) summed over the episodes still running and divided by "steps".
@@ -68,7 +68,19 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
     ``env.fear_shield_joint`` with at most ``shield_sweeps`` sweeps (the agents visited one after the other, each
     on the actions fixed so far).  The result then also carries "shield_over" [K] (the agent-steps, counted as
     the other two, whose applied action's FeAR exceeds tau: flag bit 2) and "shield_unconverged" (the env-steps
-    whose last sweep still changed an action: flag bit 3)."""
+    whose last sweep still changed an action: flag bit 3).
+    shield_crash (default off): the crash-aware shield.  The loop becomes actor -> (``env.fear_preview``) ->
+    ``env.step_preview`` -> ``env.fear_shield`` -> ``env.step``, the shield called with the preview's "safe_mask"
+    (the action mask without the actions under which the agent itself would crash) in the action mask's place.
+    With ``shield=None`` the FeAR table is a zero table allocated once and tau = 0: only crashing proposals are
+    replaced, by the most probable safe action.  The result also carries "shield_crash_proposed" [K] and
+    "shield_crash_replaced" [K] (int64 CPU tensors): the agent-steps of the episodes still running whose proposed
+    action would have crashed the agent itself / of those, the ones the shield replaced, beside
+    "shield_replaced" and "shield_stuck".  Unilateral like the FeAR shield: an agent moved to a safe action is
+    crash-free only in envs where every other agent's action was kept.  With ``shield_mode="joint"`` it raises
+    ValueError."""
+    if shield_crash and shield_mode == "joint":
+        raise ValueError('evaluate(shield_crash=True) with shield_mode="joint": the crash-aware shield is unilateral')
     if shield_mode not in ("unilateral", "joint"):
         raise ValueError('evaluate(shield_mode=...): "unilateral" or "joint"')
     joint_mode = shield is not None and shield_mode == "joint"
@@ -115,6 +127,9 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             fp_counts = torch.zeros((2, 9, (2 * int(resp_footprint) + 1) ** 2 + 1, 10, 10), dtype=torch.int64, device=dev)
             fp_visits = torch.zeros(9, dtype=torch.int64, device=dev)
         table = torch.empty((episodes, env.K, 9), dtype=torch.float64, device=dev) if shield is not None else None
+        if shield_crash and shield is None:  # a zero table under tau = 0: only the safe mask decides
+            table = torch.zeros((episodes, env.K, 9), dtype=torch.float64, device=dev)
+        crash_cnt = torch.zeros((2, env.K), dtype=torch.int64, device=dev)  # crashing proposals, of those replaced
         # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
         shield_cnt = torch.zeros((4 if joint_mode else 2, env.K), dtype=torch.int64, device=dev)
         recorded = []
@@ -130,11 +145,21 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
                 on = active.to(torch.int64).unsqueeze(1)
                 for b in range(4):
                     shield_cnt[b] += (((flags >> b) & 1) * on).sum(0)
-            elif shield is not None:  # actor -> preview -> shield -> step; the episodes still running are counted
-                env.fear_preview(actions, out=table)
-                actions, flags = env.fear_shield(table, actions, mask=env.out["mask"], probs=probs.contiguous(),
-                                                 tau=float(shield))
+            elif shield is not None or shield_crash:
+                # actor -> preview(s) -> shield -> step; the episodes still running are counted
                 on = active.to(torch.int64).unsqueeze(1)
+                amask, proposed = env.out["mask"], actions
+                if shield is not None:
+                    env.fear_preview(actions, out=table)
+                if shield_crash:  # the shield picks among the actions under which the agent itself does not crash
+                    sp = env.step_preview(actions, None, mask=amask, reward=False)
+                    amask = sp["safe_mask"]
+                    bad = (sp["crash9"].to(torch.int64) >> proposed.to(torch.int64)) & 1
+                actions, flags = env.fear_shield(table, actions, mask=amask, probs=probs.contiguous(),
+                                                 tau=0.0 if shield is None else float(shield))
+                if shield_crash:
+                    crash_cnt[0] += (bad * on).sum(0)
+                    crash_cnt[1] += (bad * (actions != proposed).to(torch.int64) * on).sum(0)
                 shield_cnt[0] += ((flags & 1) * on).sum(0)
                 shield_cnt[1] += ((flags >> 1) * on).sum(0)
             if record_actions:
@@ -194,7 +219,9 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
             from .resp_footprint import resp_footprint_from_counts
             out["resp_footprint_counts"], out["resp_footprint_visits"] = fp_counts.cpu(), fp_visits.cpu()
             out["resp_footprint"] = resp_footprint_from_counts(out["resp_footprint_counts"])[0]
-        if shield is not None:
+        if shield_crash:
+            out["shield_crash_proposed"], out["shield_crash_replaced"] = crash_cnt[0].cpu(), crash_cnt[1].cpu()
+        if shield is not None or shield_crash:
             out["shield_replaced"], out["shield_stuck"] = shield_cnt[0].cpu(), shield_cnt[1].cpu()
             if joint_mode:
                 out["shield_over"], out["shield_unconverged"] = shield_cnt[2].cpu(), int(shield_cnt[3, 0])

@@ -213,7 +213,7 @@ class Rollout:
                  patch_async: bool | None = None, desc_ring: bool | str = False, resp_matrix: bool = False,
                  fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
                  shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2,
-                 resp_map: bool = False, resp_footprint: int | None = None):
+                 resp_map: bool = False, resp_footprint: int | None = None, shield_crash: bool = False):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -290,7 +290,14 @@ class Rollout:
         keep their proposed actions) or "joint": the one call ``env.fear_shield_joint`` (the agents visited one
         after the other, at most ``shield_sweeps`` sweeps); ``shield_table`` then holds the [E, K, 9] FeAR table
         of the joint action the step applies, ``shield_flags`` carries bits 2 (over tau) and 3 (unconverged)
-        too, and ``totals()`` also carries "shield_over" [K] and "shield_unconverged"."""
+        too, and ``totals()`` also carries "shield_over" [K] and "shield_unconverged".
+        shield_crash (default off): the crash-aware shield.  The loop becomes actor -> (FeAR preview) ->
+        ``env.step_preview`` -> ``env.fear_shield`` -> step, the shield called with the preview's "safe_mask" (the
+        action mask without the actions under which the agent itself would crash) in the action mask's place.
+        With ``shield=None`` the FeAR table is a zero table allocated once and tau = 0: only crashing proposals
+        are replaced, by the most probable safe action.  ``shield_crash9`` holds the last step's [E, K] own-crash
+        sets.  Unilateral like the FeAR shield: an agent moved to a safe action is crash-free only in envs where
+        every other agent's action was kept.  With ``shield_mode="joint"`` it raises ValueError."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -417,21 +424,32 @@ class Rollout:
         self.shield = None if shield is None else float(shield)
         self.shield_flags = None  # the last step's [E, K] uint8 flags (VecGridEnv.fear_shield)
         self._shield_cnt = None
-        if shield_mode not in ("unilateral", "joint"):
-            raise ValueError('Rollout(shield_mode=...): "unilateral" or "joint"')
+        self.check_shield_args(shield_mode, shield_crash)
         self.shield_mode, self.shield_sweeps = shield_mode, int(shield_sweeps)
         self.shield_table = None  # joint mode: the last step's [E, K, 9] table of the applied joint action
-        if self.shield is not None:
+        self.shield_crash = bool(shield_crash)
+        self.shield_crash9 = None  # shield_crash: the last step's [E, K] int16 own-crash sets (env.step_preview)
+        if self.shield is not None or self.shield_crash:
             # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
             self._shield_cnt = torch.zeros((4 if shield_mode == "joint" else 2, env.K), dtype=torch.int64,
                                            device=env.device)
-            self._shield_table = torch.empty((env.E, env.K, 9), dtype=torch.float64, device=env.device)
+            # shield_crash alone: a zero table under tau = 0, so that only the safe mask decides
+            self._shield_table = (torch.zeros if self.shield is None else torch.empty)(
+                (env.E, env.K, 9), dtype=torch.float64, device=env.device)
             self._shield_out = torch.empty((env.E, env.K), dtype=torch.int32, device=env.device)
             self.shield_flags = torch.zeros((env.E, env.K), dtype=torch.uint8, device=env.device)
             if shield_mode == "joint":
                 self.shield_table = self._shield_table
             else:  # the preview's joint action: the random policy's proposals are read from it
                 self._shield_joint = torch.empty((env.E, env.N), dtype=torch.int32, device=env.device)
+
+    @staticmethod
+    def check_shield_args(shield_mode: str, shield_crash: bool):
+        """The shield keywords' checks (no device needed)."""
+        if shield_mode not in ("unilateral", "joint"):
+            raise ValueError('Rollout(shield_mode=...): "unilateral" or "joint"')
+        if shield_crash and shield_mode == "joint":
+            raise ValueError('Rollout(shield_crash=True) with shield_mode="joint": the crash-aware shield is unilateral')
 
     def _shielded(self, actions, probs, mask):
         """actor -> preview -> shield: the actions the step will apply, and the flags into the totals."""
@@ -443,12 +461,19 @@ class Rollout:
             for b in range(4):
                 self._shield_cnt[b] += ((flags >> b) & 1).sum(0)
             return out
-        if actions is None:  # the device-random policy: the preview reports the actions the step would draw
-            env.fear_preview(None, out=self._shield_table, actions=self._shield_joint)
-            actions = self._shield_joint[:, :env.K].contiguous()
-        else:
-            env.fear_preview(actions, out=self._shield_table)
-        out, flags = env.fear_shield(self._shield_table, actions, mask=mask, probs=probs, tau=self.shield,
+        if self.shield is not None:
+            if actions is None:  # the device-random policy: the preview reports the actions the step would draw
+                env.fear_preview(None, out=self._shield_table, actions=self._shield_joint)
+                actions = self._shield_joint[:, :env.K].contiguous()
+            else:
+                env.fear_preview(actions, out=self._shield_table)
+        if self.shield_crash:  # the shield picks among the actions under which the agent itself does not crash
+            sp = env.step_preview(actions, None, mask=mask, reward=False)
+            if actions is None:
+                actions = sp["actions"][:, :env.K].contiguous()
+            mask, self.shield_crash9 = sp["safe_mask"], sp["crash9"]
+        out, flags = env.fear_shield(self._shield_table, actions, mask=mask, probs=probs,
+                                     tau=0.0 if self.shield is None else self.shield,
                                      out=self._shield_out, flags=self.shield_flags)
         self._shield_cnt[0] += (flags & 1).sum(0)
         self._shield_cnt[1] += (flags >> 1).sum(0)
@@ -648,7 +673,7 @@ class Rollout:
             actions, probs = self.actors.act(self._obs_now(), mask, self.training, generator=self.gen)
         else:
             actions, probs = None, None  # device-RNG random policy
-        if self.shield is not None:  # beside the previous step's FeAR kernels (the preview has its own record buffer)
+        if self.shield is not None or self.shield_crash:  # beside the previous step's FeAR kernels (own record buffers)
             actions = self._shielded(actions, probs, mask)
         self._flush()  # after the actor: it overlapped the previous step's FeAR kernel
         if self._map_cells is not None:  # this step's pre-move cells (the previous step's are folded by now)
@@ -747,8 +772,8 @@ class Rollout:
         after at least one step; a ReturnGather (if any) with window == n and nothing pending.
         Nothing runs at capture: the state is untouched until the first replay."""
         env, rp = self.env, self.replay
-        if self.shield is not None:
-            raise ValueError("Rollout.capture: the responsibility shield (shield=tau) is eager-only")
+        if self.shield is not None or self.shield_crash:
+            raise ValueError("Rollout.capture: the responsibility shield (shield=tau, shield_crash) is eager-only")
         if not (self.fused and rp is not None and not self.distributed and self._dev_counter()):
             raise _lib.GwError("Rollout.capture: the fused actor, a replay ring and one rank")
         if rp.S % n:

@@ -709,6 +709,53 @@ class VecGridEnv:
                        "gw_fear_shield_joint")
         return out, flags, table
 
+    @staticmethod
+    def _check_step_preview_args(E: int, K: int, N: int, rl_actions, scripted, mask):
+        """The argument checks of ``step_preview`` that need no device: shapes and the mask's dtype."""
+        for t, n, name in ((rl_actions, E * K, "rl_actions"), (scripted, E * (N - K), "scripted")):
+            if t is not None and int(np.prod(np.shape(t))) != n:
+                raise ValueError(f"step_preview({name}=...): need {n} elements, got shape {tuple(np.shape(t))}")
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int16 or mask.numel() != E * K \
+                    or not mask.is_contiguous():
+                raise ValueError(f"step_preview(mask=...): need a contiguous torch.int16 tensor of {E * K} elements "
+                                 "(the 9-bit action masks, as StepResult.mask)")
+
+    def step_preview(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
+                     mask: torch.Tensor | None = None, reward: bool = True) -> dict:
+        """The step outcome preview (gw_step_preview): what ``step(rl_actions, scripted)`` would do under each of
+        the nine actions of each RL agent, without moving the world.  -> a dict of tensors, allocated once and
+        reused by every call:
+          "outcome" [E, K, 9] int16: bits 0-7 the crash bits of all N agents, bits 8-15 the restricted bits of the
+            real world update with agent k playing a and everybody else the action the step will apply;
+          "reward_alt" [E, K, 9] float64 (``reward=True``): the env reward that step would pay agent k, bit for bit;
+          "crash9" [E, K] int16: bit a = agent k itself crashes under a;
+          "safe_mask" [E, K] int16: ``mask & ~crash9`` (mask None: all nine), or ``mask`` where that is empty;
+          "actions" [E, N] int32: the joint action that step will apply.
+        None arguments mean what they mean for ``step``.  Works with ``fear=False``.  Changes no env state.  The
+        preview is unilateral: every entry assumes that the other agents play their proposed actions."""
+        E, K, N = self.E, self.K, self.N
+        self._check_step_preview_args(E, K, N, rl_actions, scripted, mask)
+        rl = self._as_i32(rl_actions, (E, K))
+        sa = self._as_i32(scripted, (E, N - K))
+        if mask is not None and mask.device != self.device:
+            raise ValueError(f"step_preview(mask=...): need a tensor on {self.device}")
+        buf = getattr(self, "_step_preview_out", None)
+        if buf is None:
+            i16 = dict(dtype=torch.int16, device=self.device)
+            buf = dict(outcome=torch.zeros((E, K, 9), **i16), reward_alt=None,
+                       crash9=torch.zeros((E, K), **i16), safe_mask=torch.zeros((E, K), **i16),
+                       actions=torch.zeros((E, N), dtype=torch.int32, device=self.device))
+            self._step_preview_out = buf
+        if reward and buf["reward_alt"] is None:
+            buf["reward_alt"] = torch.zeros((E, K, 9), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_step_preview(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), _ptr(buf["outcome"]),
+                                                _ptr(buf["reward_alt"]) if reward else None, _ptr(buf["crash9"]),
+                                                _ptr(buf["safe_mask"]), _ptr(buf["actions"]), self._stream()),
+                       "gw_step_preview")
+        return {n: t for n, t in buf.items() if t is not None and (reward or n != "reward_alt")}
+
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
         """Egocentric local observations (gw_obs_patch): [K, E, size, size] float32, agent k's obs
