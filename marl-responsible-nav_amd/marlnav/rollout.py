@@ -28,6 +28,7 @@ import torch.distributed as dist
 from . import _lib
 from .actor import MultiAgentActors
 from .parallel import shard  # noqa: F401  (re-exported)
+from .resp_folds import Shield, build_folds, check_shield_args, fold_parts, fold_results
 from .vec_env import VecGridEnv
 
 
@@ -244,60 +245,25 @@ class Rollout:
         (gw_replay_gather_desc_patch, bit for bit the writer's windows).  ``capture`` works; ``resume()``
         keeps serving descriptor rows (the carried-over obs becomes its slot's terminal half).  The CNN
         head keeps the dense window ring: its listing shares the window writer's launch.
-        resp_matrix (an env built with ``fear_rows=True``): every step's per-pair responsibility rows
-        (StepResult.fear_row) are summed over the envs into a running [K, N] total
-        (gw_fear_row_accum, one launch per step, also inside ``capture`` graphs); ``totals()`` then
-        carries "resp" and "resp_steps".
-        fear_regret (an env built with ``fear_alt=True``): every step's hindsight FeAR regret,
-        fear[e, k] - min_a fear_alt[e, k, a], and the count of envs whose agent k took a FeAR-minimal
-        action are summed over the envs (gw_fear_regret_accum, one launch per step, also inside
-        ``capture`` graphs); ``totals()`` then carries "fear_regret" [K], "fear_best" [K] and
-        "fear_regret_steps".
-        feal (an env built with ``feal=True``): every step's per-agent FeAL (StepResult.feal) is summed
-        over the envs into a running [N] total (gw_feal_accum, one launch per step, also inside
-        ``capture`` graphs); ``totals()`` then carries "feal_sum" [N], "feal_envs" (the env-steps
-        summed, over all ranks) and "feal_steps".
-        resp_full (an env built with ``fear_full=True``): every step's N x N responsibility matrix
-        (StepResult.resp_full, every world agent as actor) is summed over the envs into a running [N, N]
-        total (gw_fear_row_accum with K = N, one launch per step, also inside ``capture`` graphs);
-        ``totals()`` then carries "resp_full" and "resp_full_steps".
-        resp_map (an env built with ``fear_full=True``; turns ``resp_full`` on): where on the grid the agents
-        restrict each other.  The agents' cells are copied before every step (``env.copy_pos``, N * E int32)
-        and the step's valid-action sets are binned by them after the FeAR fence, where ``resp_full`` is
-        folded (gw_resp_map_accum, one launch per step, also inside ``capture`` graphs, under the rule
-        ``resp_full`` follows there); ``totals()`` then carries "resp_map_counts" (int64 [2, H*W, 10, 10]:
-        plane 0 caused at the actor's cell, plane 1 received at the affected agent's cell), "resp_map_visits"
-        (int64 [H*W], agent-steps per cell) and the derived "resp_map" ([2, H, W] f64, the summed Resp per
-        cell: ``marlnav.resp_map_from_counts``).  The device keeps integer counts, so the totals are the same
-        bit for bit eager or replayed, and several ranks all-reduce the integers.
-        resp_footprint (a radius R in 1..15; None: off; an env built with ``fear_full=True`` and ``debug=True``,
-        whose steps report ``actions`` and ``crash_bits``): how far, and in which direction, an action restricts
-        others.  The cells are copied before every step as for ``resp_map`` and the step's sets are binned by
-        the actor's action and the affected agent's offset from it where ``resp_map`` is folded
-        (gw_resp_footprint_accum, one launch per step, under the same rule inside ``capture`` graphs), the
-        affected agents that crashed in the step into a second plane; ``totals()`` then carries
-        "resp_footprint_counts" (int64 [2, 9, O, 10, 10], O = (2R + 1)^2 + 1: the near offsets row-major, then
-        the far bin), "resp_footprint_visits" (int64 [9], actor-steps per action) and the derived
-        "resp_footprint" ([2, 9, O] f64, the summed Resp per action and offset:
-        ``marlnav.resp_footprint_from_counts``).  Integer counts, all-reduced as integers.
-        shield (a float tau; None: off, no extra launch): the responsibility shield.  Every step runs actor,
-        then ``env.fear_preview`` of the proposed actions, then ``env.fear_shield`` (the env's action mask, the
-        actor's probabilities, every RL agent shielded), then ``env.step`` with the shielded actions.  The ring
-        keeps the actor's probabilities unchanged (the reference stores ``cont_actions``).  ``shield_flags``
-        holds the last step's [E, K] flags and ``totals()`` carries "shield_replaced" [K] and "shield_stuck"
-        [K].  Eager only: ``capture`` raises ValueError.  Works with FeAR off (``fear=False``) too.
-        shield_mode: "unilateral" (the default: the two calls above, each agent's row assuming that the others
-        keep their proposed actions) or "joint": the one call ``env.fear_shield_joint`` (the agents visited one
-        after the other, at most ``shield_sweeps`` sweeps); ``shield_table`` then holds the [E, K, 9] FeAR table
-        of the joint action the step applies, ``shield_flags`` carries bits 2 (over tau) and 3 (unconverged)
-        too, and ``totals()`` also carries "shield_over" [K] and "shield_unconverged".
-        shield_crash (default off): the crash-aware shield.  The loop becomes actor -> (FeAR preview) ->
-        ``env.step_preview`` -> ``env.fear_shield`` -> step, the shield called with the preview's "safe_mask" (the
-        action mask without the actions under which the agent itself would crash) in the action mask's place.
-        With ``shield=None`` the FeAR table is a zero table allocated once and tau = 0: only crashing proposals
-        are replaced, by the most probable safe action.  ``shield_crash9`` holds the last step's [E, K] own-crash
-        sets.  Unilateral like the FeAR shield: an agent moved to a safe action is crash-free only in envs where
-        every other agent's action was kept.  With ``shield_mode="joint"`` it raises ValueError."""
+        The responsibility folds (marlnav/resp_folds.py: each class says what it sums): one launch each per
+        step after the FeAR fence, also inside ``capture`` graphs; an env without the flag raises ValueError.
+          resp_matrix: ``RowFold``, env ``fear_rows=True``; totals "resp" [K, N], "resp_steps".
+          fear_regret: ``RegretFold``, env ``fear_alt=True``; "fear_regret" [K], "fear_best" [K], "fear_regret_steps".
+          feal: ``FealFold``, env ``feal=True``; "feal_sum" [N], "feal_envs", "feal_steps".
+          resp_full: ``RowFold`` with K = N, env ``fear_full=True``; "resp_full" [N, N], "resp_full_steps".
+          resp_map (turns ``resp_full`` on): ``MapFold``, env ``fear_full=True``; the agents' cells are copied
+            before every step (``env.copy_pos``); "resp_map_counts", "resp_map_visits", "resp_map" [2, H, W].
+          resp_footprint (a radius R in 1..15; None: off): ``FootprintFold``, env ``fear_full=True`` and
+            ``debug=True``; "resp_footprint_counts", "resp_footprint_visits", "resp_footprint" [2, 9, O].
+        The responsibility shield between the actor and the step (``resp_folds.Shield`` has the pipelines):
+          shield (a float tau; None: off, no extra launch): ``shield_flags`` holds the last step's [E, K] flags;
+            totals "shield_replaced" [K], "shield_stuck" [K].  Works with FeAR off too.  The ring keeps the
+            actor's probabilities unchanged (the reference stores ``cont_actions``).
+          shield_mode: "unilateral" or "joint" (at most ``shield_sweeps`` sweeps); joint: ``shield_table`` holds
+            the [E, K, 9] table of the applied joint action; also "shield_over" [K], "shield_unconverged".
+          shield_crash: the crash-aware shield, alone or with ``shield``; ``shield_crash9`` holds the last
+            step's [E, K] own-crash sets.  Unilateral: ValueError with ``shield_mode="joint"``.
+        Eager only: ``capture`` raises ValueError."""
         self.env = env
         self.actors = actors
         self.fused = (actors is not None and actors.fusable(env, patch)) if fused is None else bool(fused)
@@ -373,111 +339,20 @@ class Rollout:
             raise ValueError("ReturnGather shard size != env.E")
         env.set_obs_async(obs_async, fear_async=fear_async)
         self._pending = None  # (stats, tick) of a step whose FeAR may still be in flight
-        self._resp = self._resp_steps = None
-        if resp_matrix:
-            if env.out.get("fear_row") is None:
-                raise ValueError("Rollout(resp_matrix=True) needs VecGridEnv(fear_rows=True)")
-            self._resp = torch.zeros((env.K, env.N), dtype=torch.float64, device=env.device)
-            self._resp_steps = torch.zeros((), dtype=torch.int64, device=env.device)
-        self._regret = self._regret_steps = None
-        if fear_regret:
-            if env.out.get("fear_alt") is None:
-                raise ValueError("Rollout(fear_regret=True) needs VecGridEnv(fear_alt=True)")
-            self._regret = torch.zeros((env.K, 2), dtype=torch.float64, device=env.device)
-            self._regret_steps = torch.zeros((), dtype=torch.int64, device=env.device)
-        self._feal = self._feal_cnt = None
-        if feal:
-            if env.out.get("feal") is None:
-                raise ValueError("Rollout(feal=True) needs VecGridEnv(feal=True)")
-            self._feal = torch.zeros(env.N, dtype=torch.float64, device=env.device)
-            self._feal_cnt = torch.zeros(2, dtype=torch.int64, device=env.device)  # steps, env-steps
-        self._map_counts = self._map_visits = self._map_cells = None
-        if resp_map:
-            if env.out.get("resp_valid") is None:
-                raise ValueError("Rollout(resp_map=True) needs VecGridEnv(fear_full=True)")
-            resp_full = True
-            hw = env.H * env.W
-            self._map_counts = torch.zeros((2, hw, 10, 10), dtype=torch.int64, device=env.device)
-            self._map_visits = torch.zeros(hw, dtype=torch.int64, device=env.device)
-            self._map_cells = torch.empty((env.N, env.E), dtype=torch.int32, device=env.device)
-        self._fp_counts = self._fp_visits = None
-        self._fp_radius = None if resp_footprint is None else int(resp_footprint)
-        if self._fp_radius is not None:
-            if env.out.get("resp_valid") is None:
-                raise ValueError("Rollout(resp_footprint=R) needs VecGridEnv(fear_full=True)")
-            if env.out.get("actions") is None or env.out.get("crash_bits") is None:
-                raise ValueError("Rollout(resp_footprint=R) needs VecGridEnv(debug=True) (the step's actions and "
-                                 "crash_bits)")
-            if not 1 <= self._fp_radius <= 15:
-                raise ValueError("Rollout(resp_footprint=R): R in 1..15")
-            n_off = (2 * self._fp_radius + 1) ** 2 + 1
-            self._fp_counts = torch.zeros((2, 9, n_off, 10, 10), dtype=torch.int64, device=env.device)
-            self._fp_visits = torch.zeros(9, dtype=torch.int64, device=env.device)
-            if self._map_cells is None:
-                self._map_cells = torch.empty((env.N, env.E), dtype=torch.int32, device=env.device)
-        self._full = self._full_steps = None
-        if resp_full:
-            if env.out.get("resp_full") is None:
-                raise ValueError("Rollout(resp_full=True) needs VecGridEnv(fear_full=True)")
-            self._full = torch.zeros((env.N, env.N), dtype=torch.float64, device=env.device)
-            self._full_steps = torch.zeros((), dtype=torch.int64, device=env.device)
-        self.shield = None if shield is None else float(shield)
-        self.shield_flags = None  # the last step's [E, K] uint8 flags (VecGridEnv.fear_shield)
-        self._shield_cnt = None
+        self._folds, self._cells = build_folds(env, "Rollout", resp_matrix, fear_regret, feal, resp_full, resp_map,
+                                               resp_footprint)
         self.check_shield_args(shield_mode, shield_crash)
-        self.shield_mode, self.shield_sweeps = shield_mode, int(shield_sweeps)
-        self.shield_table = None  # joint mode: the last step's [E, K, 9] table of the applied joint action
-        self.shield_crash = bool(shield_crash)
-        self.shield_crash9 = None  # shield_crash: the last step's [E, K] int16 own-crash sets (env.step_preview)
+        self.shield = None if shield is None else float(shield)
+        self.shield_mode, self.shield_sweeps, self.shield_crash = shield_mode, int(shield_sweeps), bool(shield_crash)
+        self._shield = None
         if self.shield is not None or self.shield_crash:
-            # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
-            self._shield_cnt = torch.zeros((4 if shield_mode == "joint" else 2, env.K), dtype=torch.int64,
-                                           device=env.device)
-            # shield_crash alone: a zero table under tau = 0, so that only the safe mask decides
-            self._shield_table = (torch.zeros if self.shield is None else torch.empty)(
-                (env.E, env.K, 9), dtype=torch.float64, device=env.device)
-            self._shield_out = torch.empty((env.E, env.K), dtype=torch.int32, device=env.device)
-            self.shield_flags = torch.zeros((env.E, env.K), dtype=torch.uint8, device=env.device)
-            if shield_mode == "joint":
-                self.shield_table = self._shield_table
-            else:  # the preview's joint action: the random policy's proposals are read from it
-                self._shield_joint = torch.empty((env.E, env.N), dtype=torch.int32, device=env.device)
+            self._shield = Shield(env, self.shield, shield_mode, shield_sweeps, self.shield_crash)
 
-    @staticmethod
-    def check_shield_args(shield_mode: str, shield_crash: bool):
-        """The shield keywords' checks (no device needed)."""
-        if shield_mode not in ("unilateral", "joint"):
-            raise ValueError('Rollout(shield_mode=...): "unilateral" or "joint"')
-        if shield_crash and shield_mode == "joint":
-            raise ValueError('Rollout(shield_crash=True) with shield_mode="joint": the crash-aware shield is unilateral')
+    check_shield_args = staticmethod(check_shield_args)
 
-    def _shielded(self, actions, probs, mask):
-        """actor -> preview -> shield: the actions the step will apply, and the flags into the totals."""
-        env = self.env
-        if self.shield_mode == "joint":  # the one call; None actions: the draws the step would make
-            out, flags, _ = env.fear_shield_joint(actions, None, mask=mask, probs=probs, tau=self.shield,
-                                                  sweeps=self.shield_sweeps, out=self._shield_out,
-                                                  flags=self.shield_flags, table=self._shield_table)
-            for b in range(4):
-                self._shield_cnt[b] += ((flags >> b) & 1).sum(0)
-            return out
-        if self.shield is not None:
-            if actions is None:  # the device-random policy: the preview reports the actions the step would draw
-                env.fear_preview(None, out=self._shield_table, actions=self._shield_joint)
-                actions = self._shield_joint[:, :env.K].contiguous()
-            else:
-                env.fear_preview(actions, out=self._shield_table)
-        if self.shield_crash:  # the shield picks among the actions under which the agent itself does not crash
-            sp = env.step_preview(actions, None, mask=mask, reward=False)
-            if actions is None:
-                actions = sp["actions"][:, :env.K].contiguous()
-            mask, self.shield_crash9 = sp["safe_mask"], sp["crash9"]
-        out, flags = env.fear_shield(self._shield_table, actions, mask=mask, probs=probs,
-                                     tau=0.0 if self.shield is None else self.shield,
-                                     out=self._shield_out, flags=self.shield_flags)
-        self._shield_cnt[0] += (flags & 1).sum(0)
-        self._shield_cnt[1] += (flags >> 1).sum(0)
-        return out
+    # the shield's last-step tensors (None without a shield / outside the mode that fills them)
+    shield_flags, shield_table, shield_crash9 = (property(lambda self, n=n: getattr(self._shield, n, None))
+                                                 for n in ("flags", "table", "crash9"))
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0
@@ -496,37 +371,8 @@ class Rollout:
             self._reduce(stats, tick)
 
     def _reduce(self, stats, tick):
-        if self._resp is not None:  # the step's Resp rows (FeAR-owned: fenced by the caller) into the total
-            env = self.env
-            _lib.check(env.lib.gw_fear_row_accum(env.out["fear_row"].data_ptr(), None, env.E, env.K, env.N,
-                                                 self._resp.data_ptr(), self._resp_steps.data_ptr(),
-                                                 torch.cuda.current_stream(env.device).cuda_stream),
-                       "gw_fear_row_accum")
-        if self._regret is not None:  # the step's per-action table against its fear (both FeAR-owned)
-            env = self.env
-            _lib.check(env.lib.gw_fear_regret_accum(env.out["fear_alt"].data_ptr(), env.out["fear"].data_ptr(), None,
-                                                    env.E, env.K, self._regret.data_ptr(),
-                                                    self._regret_steps.data_ptr(),
-                                                    torch.cuda.current_stream(env.device).cuda_stream),
-                       "gw_fear_regret_accum")
-        if self._feal is not None:  # the step's per-agent FeAL (FeAR-owned as well)
-            env = self.env
-            cnt = self._feal_cnt.data_ptr()
-            _lib.check(env.lib.gw_feal_accum(env.out["feal"].data_ptr(), None, env.E, env.N, self._feal.data_ptr(),
-                                             cnt, cnt + 8, torch.cuda.current_stream(env.device).cuda_stream),
-                       "gw_feal_accum")
-        if self._full is not None:  # the step's N x N matrix (FeAR-owned): the row fold with every agent an actor
-            env = self.env
-            _lib.check(env.lib.gw_fear_row_accum(env.out["resp_full"].data_ptr(), None, env.E, env.N, env.N,
-                                                 self._full.data_ptr(), self._full_steps.data_ptr(),
-                                                 torch.cuda.current_stream(env.device).cuda_stream),
-                       "gw_fear_row_accum")
-        if self._map_counts is not None:  # the step's sets (FeAR-owned) binned by the cells copied before it
-            self.env.resp_map_accum(self.env.out["resp_valid"], self._map_cells, self._map_counts, self._map_visits)
-        if self._fp_counts is not None:  # the same sets by the actor's action and the affected agent's offset
-            out = self.env.out
-            self.env.resp_footprint_accum(out["resp_valid"], self._map_cells, out["actions"], self._fp_counts,
-                                          self._fp_visits, crash_bits=out["crash_bits"], radius=self._fp_radius)
+        for f in self._folds:  # the step's FeAR-owned outputs (fenced by the caller) into the totals
+            f.fold(self.env, self.env.out)
         if self.gather is not None:
             self.gather.push()  # the step wrote ep_return / done into the gather's send buffer
         if self._acc is not None:
@@ -673,11 +519,11 @@ class Rollout:
             actions, probs = self.actors.act(self._obs_now(), mask, self.training, generator=self.gen)
         else:
             actions, probs = None, None  # device-RNG random policy
-        if self.shield is not None or self.shield_crash:  # beside the previous step's FeAR kernels (own record buffers)
-            actions = self._shielded(actions, probs, mask)
+        if self._shield is not None:  # beside the previous step's FeAR kernels (own record buffers)
+            actions = self._shield.apply(env, actions, probs, mask)
         self._flush()  # after the actor: it overlapped the previous step's FeAR kernel
-        if self._map_cells is not None:  # this step's pre-move cells (the previous step's are folded by now)
-            env.copy_pos(self._map_cells)
+        if self._cells is not None:  # this step's pre-move cells (the previous step's are folded by now)
+            env.copy_pos(self._cells)
         if self.replay is not None:
             rp = self.replay
             nxt = (self.t + 1) % rp.S
@@ -772,7 +618,7 @@ class Rollout:
         after at least one step; a ReturnGather (if any) with window == n and nothing pending.
         Nothing runs at capture: the state is untouched until the first replay."""
         env, rp = self.env, self.replay
-        if self.shield is not None or self.shield_crash:
+        if self._shield is not None:
             raise ValueError("Rollout.capture: the responsibility shield (shield=tau, shield_crash) is eager-only")
         if not (self.fused and rp is not None and not self.distributed and self._dev_counter()):
             raise _lib.GwError("Rollout.capture: the fused actor, a replay ring and one rank")
@@ -826,96 +672,30 @@ class Rollout:
     def totals(self) -> dict:
         """Episode statistics summed over all steps (and ranks): completed-episode return sum,
         episodes, FeAR, crashes, apples, shaped reward, completed-episode length sum, env-steps.
-        With ``resp_matrix``: "resp", the [K, N] sum of every step's and env's responsibility rows
-        (f64 CPU tensor), and "resp_steps", the steps it covers.
-        With ``fear_regret``: "fear_regret" [K] (the summed hindsight FeAR regret), "fear_best" [K] (env-steps
-        in which agent k's action was FeAR-minimal) and "fear_regret_steps".
-        With ``feal``: "feal_sum" [N] (every step's and env's FeAL per world agent, f64 CPU tensor),
-        "feal_envs" (the env-steps it sums: feal_sum / feal_envs is the mean FeAL) and "feal_steps".
-        With ``resp_full``: "resp_full", the [N, N] sum of every step's and env's responsibility matrix
-        (f64 CPU tensor, all-reduced with the rest), and "resp_full_steps", this rank's steps (like
-        "resp_steps": the ranks step in lockstep, so the count is not summed over them).
-        With ``resp_map``: "resp_map_counts" (int64 [2, H*W, 10, 10] CPU tensor, summed over the ranks in an
-        integer all-reduce of its own), "resp_map_visits" (int64 [H*W]) and "resp_map" ([2, H, W] f64:
-        ``marlnav.resp_map_from_counts`` of the counts; plane 0 the Resp caused at a cell, plane 1 received).
-        With ``resp_footprint``: "resp_footprint_counts" (int64 [2, 9, O, 10, 10] CPU tensor, all-reduced as
-        integers), "resp_footprint_visits" (int64 [9]) and "resp_footprint" ([2, 9, O] f64:
-        ``marlnav.resp_footprint_from_counts`` of the counts; plane 1 the affected agents that crashed).
-        With ``shield``: "shield_replaced" [K] and "shield_stuck" [K] (int64 CPU tensors): the agent-steps whose
-        action the shield replaced (flag bit 0) / that had no allowed action (flag bit 1).  With
-        ``shield_mode="joint"`` also "shield_over" [K] (agent-steps whose applied action's FeAR exceeds tau, flag
-        bit 2) and "shield_unconverged" (env-steps whose last sweep still changed an action, flag bit 3).
-        With several ranks this is a collective (one all-reduce of 8 doubles, plus the K * N of
-        the responsibility total): every rank calls it."""
-        if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
-                and self._full is None and self._shield_cnt is None and self._fp_counts is None):
+        With the responsibility folds and the shield armed: their keys too (``Rollout.__init__`` lists them;
+        f64 / int64 CPU tensors and ints).  The folds' step counts ("resp_steps", ...) are this rank's: the
+        ranks step in lockstep, so they are not summed over them.
+        With several ranks this is a collective: every rank calls it.  In order: the shield's counts (one
+        integer all-reduce), one float64 all-reduce of the 8 statistics and the folds' float64 totals, then
+        an integer all-reduce each for the map's and the footprint's counts and visits."""
+        if self._acc is None and not self._folds and self._shield is None:
             return {}
-        if self._shield_cnt is not None:  # its own small all-reduce: exact integer counts
-            cnt = self._shield_cnt.clone()
-            if self.distributed:
-                dist.all_reduce(cnt, group=self.group)
-            shield = {"shield_replaced": cnt[0].cpu(), "shield_stuck": cnt[1].cpu()}
-            if self.shield_mode == "joint":
-                shield["shield_over"], shield["shield_unconverged"] = cnt[2].cpu(), int(cnt[3, 0])
-            if (self._acc is None and self._resp is None and self._regret is None and self._feal is None
-                    and self._full is None and self._fp_counts is None):
-                self._flush()
-                return shield
-        else:
-            shield = {}
+        reduce = (lambda t: dist.all_reduce(t, group=self.group)) if self.distributed else None
+        shield = self._shield.totals(reduce) if self._shield is not None else {}
         self._flush()
+        if self._acc is None and not self._folds:
+            return shield
         nst = _lib.GW_STATS if self._acc is not None else 0
-        parts = [self._acc.sum(0)] if nst else []
-        if self._resp is not None:  # all-reduced with the other statistics, in the same collective
-            parts.append(self._resp.reshape(-1))
-        if self._regret is not None:
-            parts.append(self._regret.reshape(-1))
-        if self._feal is not None:  # the env-step count rides along as a double (exact below 2^53)
-            parts.append(self._feal)
-            parts.append(self._feal_cnt[1:2].to(torch.float64))
-        if self._full is not None:
-            parts.append(self._full.reshape(-1))
-        if not parts:  # only the footprint's integer counts below
+        parts, widths = fold_parts(self._folds)
+        if nst:
+            parts.insert(0, self._acc.sum(0))
+        if not parts:  # only integer counts below
             parts.append(torch.zeros(0, dtype=torch.float64, device=self.env.device))
         local = torch.cat(parts) if len(parts) > 1 else parts[0].clone()  # (the all-reduce is in place)
         if self.distributed and local.numel():
             dist.all_reduce(local, group=self.group)
         out = dict(zip(_lib.STATS_NAMES, local[:nst].cpu().tolist()))
-        if self._resp is not None:
-            out["resp"] = local[nst:nst + self.env.K * self.env.N].reshape(self.env.K, self.env.N).cpu()
-            out["resp_steps"] = int(self._resp_steps)  # this rank's steps (the ranks step in lockstep)
-            nst += self.env.K * self.env.N
-        if self._regret is not None:
-            reg = local[nst:nst + 2 * self.env.K].reshape(self.env.K, 2).cpu()
-            out["fear_regret"], out["fear_best"] = reg[:, 0].clone(), reg[:, 1].clone()
-            out["fear_regret_steps"] = int(self._regret_steps)
-            nst += 2 * self.env.K
-        if self._feal is not None:
-            N = self.env.N
-            out["feal_sum"] = local[nst:nst + N].cpu()
-            out["feal_envs"] = int(local[nst + N])
-            out["feal_steps"] = int(self._feal_cnt[0])
-            nst += N + 1
-        if self._full is not None:
-            N = self.env.N
-            out["resp_full"] = local[nst:nst + N * N].reshape(N, N).cpu()
-            out["resp_full_steps"] = int(self._full_steps)
-        if self._map_counts is not None:  # exact integer counts: their own all-reduce
-            cnt, vis = self._map_counts.clone(), self._map_visits.clone()
-            if self.distributed:
-                dist.all_reduce(cnt, group=self.group)
-                dist.all_reduce(vis, group=self.group)
-            from .resp_map import resp_map_from_counts
-            out["resp_map_counts"], out["resp_map_visits"] = cnt.cpu(), vis.cpu()
-            out["resp_map"] = resp_map_from_counts(out["resp_map_counts"])[0].reshape(2, self.env.H, self.env.W)
-        if self._fp_counts is not None:  # likewise
-            cnt, vis = self._fp_counts.clone(), self._fp_visits.clone()
-            if self.distributed:
-                dist.all_reduce(cnt, group=self.group)
-                dist.all_reduce(vis, group=self.group)
-            from .resp_footprint import resp_footprint_from_counts
-            out["resp_footprint_counts"], out["resp_footprint_visits"] = cnt.cpu(), vis.cpu()
-            out["resp_footprint"] = resp_footprint_from_counts(out["resp_footprint_counts"])[0]
+        out.update(fold_results(self._folds, widths, local[nst:], reduce))
         out.update(shield)
         return out
 
