@@ -165,7 +165,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * GW_SPAN_FEAR_FULL the N x N responsibility matrix's kernel (fear_full_kernel, gw_set_fear_full),
  * GW_SPAN_FEAR_PREVIEW the two launches of gw_fear_preview (preview_rec_kernel, fear_alt_kernel),
  * GW_SPAN_FEAR_SHIELD the two launches of gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel),
- * GW_SPAN_STEP_PREVIEW the two launches of gw_step_preview (preview_rec_kernel, step_preview_kernel).
+ * GW_SPAN_STEP_PREVIEW the two launches of gw_step_preview (preview_rec_kernel, step_preview_kernel),
+ * GW_SPAN_CRASH_SHIELD the two launches of gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -175,7 +176,8 @@ enum {
     GW_SPAN_CNN_LIST = 5, GW_SPAN_CNN_RARE = 6, GW_SPAN_WINDOW = 7, GW_SPAN_LEARN = 8,
     GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11, GW_SPAN_FEAR_PREVIEW = 12,
     GW_SPAN_FEAR_SHIELD = 13 /* the two launches of one gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel) */,
-    GW_SPAN_STEP_PREVIEW = 14 /* the two launches of one gw_step_preview (preview_rec_kernel, step_preview_kernel) */
+    GW_SPAN_STEP_PREVIEW = 14 /* the two launches of one gw_step_preview (preview_rec_kernel, step_preview_kernel) */,
+    GW_SPAN_CRASH_SHIELD = 15 /* the two launches of one gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel) */
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -514,6 +516,71 @@ gw_status gw_fear_shield_joint(void *env, const int32_t *rl_actions, const int32
 gw_status gw_step_preview(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
                           uint16_t *outcome, double *reward_alt, uint16_t *crash9, uint16_t *safe_mask,
                           int32_t *actions, void *stream);
+
+/* The coordinated crash-aware shield: gw_step_preview's safe masks inside gw_fear_shield_joint's sweeps, in one call.
+ * The crash-aware shield built from gw_step_preview and gw_fear_shield is unilateral: an agent moved to a safe action
+ * is crash-free only where every other agent's action was kept, so two agents that were both moved can still meet.
+ * Here every visit previews the agent's nine actions against the actions the agents before it have fixed.  Per env,
+ * with `scripted` the scripted agents' actions and prop[k] the proposed RL actions (given, or NULL = drawn with the
+ * step's own Philox counters; a proposal outside 0..8 is read as 0, as gw_step applies it):
+ *   cur = prop
+ *   O_prop = crash | restr << 8 of the real UpdateGWorld of the current world under (prop, scripted)
+ *   for s in 1..sweeps:
+ *     changed = false
+ *     for k in 0..K-1 ascending, where bit k of `agents` is set:
+ *       crash9 = { a : agent k ITSELF crashes in the real UpdateGWorld under (cur, scripted) with k playing a }
+ *                (gw_step_preview's task: the full joint action, eaters 0..K-1, the apples still present)
+ *       m'  = the safe mask of csrc/step_preview.h on (mask given, mask[k], crash9)
+ *       t   = use_fear ? row k of gw_fear_preview's table for (cur, scripted) : nine zeros
+ *       r   = the pick of csrc/fear_shield.h on (t, cur[k], m', probs of k, use_fear ? tau : 0.0)
+ *       stuck[k]       = bit 1 of r's flags
+ *       unavoidable[k] = the mask word of k (all nine if none) != 0 and (it & ~crash9) == 0
+ *       if r.action != cur[k]: cur[k] = r.action, changed = true
+ *     if not changed: break
+ *   O = crash | restr << 8 of the real UpdateGWorld under (cur, scripted)
+ *   T = gw_fear_preview's table for (cur, scripted)     (only if use_fear or fear_alt != NULL)
+ * The visit (m', r, unavoidable) is csrc/crash_shield.h's.  use_fear == 0 is the crash shield alone: tau is ignored,
+ * an agent that would crash is moved to its most probable action (no probs: the lowest) under which it does not,
+ * and nothing else moves.
+ * Outputs (any may be NULL except actions_out):
+ *   actions_out [E][K] = cur (may alias rl_actions);  fear_alt [E][K][9] f64 = T;  joint [E][N] = the joint action
+ *   the step will apply;  outcome [E] u16 = O;  outcome_prop [E] u16 = O_prop;  crash9 [E][K] u16 = the own-crash
+ *   sets under the FINAL joint action, gw_step_preview's crash9 for (cur, scripted);  flags [E][K] u8:
+ *     bits 0-3 as gw_fear_shield_joint's (replaced, stuck, over tau, unconverged); bit 2 is set only when use_fear;
+ *     bit 4  bit k of O: agent k crashes in the step that applies actions_out;
+ *     bit 5  unavoidable[k] of k's last visit (0 for an agent never visited).
+ * It follows that
+ *   - O[e] == crash_bits[e] | restr_bits[e] << 8 of the gw_step that applies actions_out with the same scripted
+ *     actions;
+ *   - with use_fear, T[e][k][actions_out[e][k]] is bit for bit that step's fear[e][k];
+ *   - in an env with bit 3 clear every shielded agent with a non-zero mask and bit 5 clear has bit 4 clear (the
+ *     unchanged sweep saw the final joint action, and every visit leaves the agent inside m');
+ *   - where bit 2 is clear and use_fear, that step's fear[e][k] <= tau;
+ *   - sweeps = 1, agents = 1 << k gives, for that k, the actions and flag bits 0-1 of the unilateral pipeline:
+ *     gw_fear_preview, gw_step_preview's safe_mask, gw_fear_shield(agents = 1 << k) (use_fear == 0: on a zero table
+ *     with tau = 0);
+ *   - use_fear == 0 runs no FeAR world update at all unless fear_alt is given.
+ * mask, probs, agents, sweeps as gw_fear_shield_joint's.  Its conventions too: works on cfg.fear == 0 envs; changes no
+ * env state, step output, pipeline state or obs-destination table; shares the preview's record buffer (a first call
+ * while `stream` captures returns GW_ERR_STATE, later calls can be captured); no host synchronisation; GW_ERR_STATE
+ * before the first gw_reset; GW_ERR_ARG on a null env, null actions_out or sweeps out of range.
+ * Cost: two launches on `stream` (preview_rec_kernel, then crash_shield_joint_kernel: one wave per env, every visit,
+ * the final outcome and the table in it), one GW_SPAN_CRASH_SHIELD span while profiling.  The world updates the
+ * kernel's schedule runs per env, all counted by gw_count_sims:
+ *   - a visit of agent k: 9 real updates (one per action of k), and with use_fear the 9 (1 + 8 (c_k - 1)) FeAR
+ *     updates of gw_fear_shield_joint's visit (close count c_k);
+ *   - the proposal outcome: none of its own (with no visit it is the final outcome; else nothing has moved at the
+ *     env's first visit, whose update under the agent's kept action is the proposal's);
+ *   - the final outcome and crash9: 9 K real updates, always (the update of agent 0 under cur[0] is the final
+ *     joint action's: O costs none of its own);
+ *   - the final table, only if use_fear or fear_alt != NULL: the FeAR updates of all K agents; or, when use_fear
+ *     and a sweep ran and the last one changed nothing, only those of the unshielded agents (the shielded agents'
+ *     rows are then the visits').
+ * Composed from gw_fear_preview, gw_step_preview and gw_fear_shield a visit costs three calls (six launches). */
+gw_status gw_crash_shield_joint(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                                const float *probs, int32_t use_fear, double tau, uint32_t agents, int32_t sweeps,
+                                int32_t *actions_out, uint8_t *flags, double *fear_alt, int32_t *joint,
+                                uint16_t *outcome, uint16_t *outcome_prop, uint16_t *crash9, void *stream);
 
 #ifdef __cplusplus
 }

@@ -558,6 +558,29 @@ struct ShieldJointArgs {
 hipError_t launch_fear_shield_joint(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
                                     const ShieldJointArgs &a);
 
+// gw_crash_shield_joint's arguments beside the env's (include/gridenv.h): ShieldJointArgs' plus use_fear and the
+// outputs outcome [E] / outcome_prop [E] / crash9 [E][K] or null
+struct CrashShieldArgs {
+    const uint16_t *mask;
+    const float *probs;
+    int use_fear;
+    double tau;
+    uint32_t agents;
+    int sweeps;
+    int32_t *actions_out;
+    uint8_t *flags;
+    double *table;
+    int32_t *joint;
+    uint16_t *outcome;
+    uint16_t *outcome_prop;
+    uint16_t *crash9;
+};
+
+// crash_shield_joint_kernel<N> (crash_shield_joint.hip, gw_crash_shield_joint) over p's env range on s, through
+// gwprof::launch, from the record in p.fwork
+hipError_t launch_crash_shield_joint(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
+                                     const CrashShieldArgs &a);
+
 // fear_alt_kernel<N> (fear_cf.hip; gw_set_fear_alt, and gw_fear_preview on the preview's record) over p's env
 // range on s, through gwprof::launch: table [E][K][9]
 hipError_t launch_fear_alt(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p, double *table);

@@ -1866,7 +1866,7 @@ int64_t ceil_div(int64_t n, int64_t d) { return (n + d - 1) / d; }
 size_t step_lds(const gw::Params &p, bool fear) { return (size_t)p.resp_off + (fear ? 100 * sizeof(double) : 0); }
 
 // dynamic LDS of the FeAR kernels (fear_v2, fear_rows_kernel here; through launch_cf the wave-per-env kernels
-// of fear_cf.hip, fear_full.hip and fear_shield_joint.hip): [cell table][Resp] (feal_kernel: the FeAL table in
+// of fear_cf.hip, fear_full.hip, fear_shield_joint.hip and crash_shield_joint.hip): [cell table][Resp] (feal_kernel: the FeAL table in
 // Resp's place).
 // Sets p's offsets for it and returns its size.
 size_t fear_lds(gw::Params &p) {
@@ -3025,6 +3025,37 @@ gw_status gw_fear_shield_joint(void *handle, const int32_t *rl_actions, const in
         rec = gw::launch_preview_rec(env->N, s, q, nullptr, nullptr);
         if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
         rec = gw::launch_fear_shield_joint(env->N, grid, block, dyn, s, q, a);
+    }));
+    HIP_TRY(rec);
+    return GW_OK;
+}
+
+gw_status gw_crash_shield_joint(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                                const float *probs, int32_t use_fear, double tau, uint32_t agents, int32_t sweeps,
+                                int32_t *actions_out, uint8_t *flags, double *fear_alt, int32_t *joint,
+                                uint16_t *outcome, uint16_t *outcome_prop, uint16_t *crash9, void *stream) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_crash_shield_joint: null env");
+    if (!actions_out) return fail(GW_ERR_ARG, "gw_crash_shield_joint: null actions_out");
+    if (sweeps < 1 || sweeps > GW_SHIELD_MAX_SWEEPS)
+        return fail(GW_ERR_ARG, "gw_crash_shield_joint: sweeps outside 1..GW_SHIELD_MAX_SWEEPS");
+    if (!env->initialized) return fail(GW_ERR_STATE, "gw_crash_shield_joint before gw_reset");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GW_TRY(ensure_preview_rec(env, s, "gw_crash_shield_joint"));
+    // as gw_fear_preview: the env's state as the next gw_step will read it, nothing of the env written
+    gw::Params p = make_params(env);
+    p.rl = rl_actions;
+    p.scripted = scripted;
+    p.fwork = env->preview_rec;
+    const gw::CrashShieldArgs a{mask, probs, use_fear != 0, use_fear ? tau : 0.0, agents, sweeps, actions_out,
+                                flags, fear_alt, joint, outcome, outcome_prop, crash9};
+    hipError_t rec = hipSuccess;
+    GW_TRY(launch_cf(env, GW_SPAN_CRASH_SHIELD, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        // the record of the proposed joint action, then the sweeps, the final outcome and table on it
+        // (crash_shield_joint.hip, its own code object): both launches are the one span
+        rec = gw::launch_preview_rec(env->N, s, q, nullptr, nullptr);
+        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
+        rec = gw::launch_crash_shield_joint(env->N, grid, block, dyn, s, q, a);
     }));
     HIP_TRY(rec);
     return GW_OK;

@@ -45,10 +45,14 @@ def main(argv=None):
                     help="responsibility shield: before every step, replace an RL action whose previewed FeAR "
                          "exceeds TAU by an allowed one (the most probable under the actor); also prints how many "
                          "agent-steps were replaced / had no allowed action")
-    ap.add_argument("--shield-mode", choices=["unilateral", "joint"], default="unilateral",
+    ap.add_argument("--shield-mode", choices=["unilateral", "joint", "joint_crash"], default="unilateral",
                     help="unilateral: every agent's choice assumes that the others keep their proposed actions; "
                          "joint: the agents are visited one after the other, each on the actions fixed so far, and "
-                         "the agent-steps whose applied action still exceeds TAU are printed too")
+                         "the agent-steps whose applied action still exceeds TAU are printed too; joint_crash: the "
+                         "joint visits with the crash preview in each (an agent is kept to actions under which it "
+                         "does not crash against the actions fixed so far); with --shield TAU it also shields "
+                         "FeAR, without it only crashes; prints the crashing proposals, the crashes left and the "
+                         "unavoidable ones")
     ap.add_argument("--shield-sweeps", type=int, default=2, metavar="N",
                     help="joint mode: at most N sweeps over the agents (1..8; a sweep that changes nothing ends them)")
     ap.add_argument("--shield-crash", action="store_true",
@@ -86,13 +90,21 @@ def main(argv=None):
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
     print(f"Total steps: {r['steps']} across {n} episodes")
+    joint_crash = args.shield_mode == "joint_crash"
+    if joint_crash and args.shield is None:
+        print(f"Shield (crashes only): replaced {r['shield_replaced'].tolist()} agent-steps per RL agent")
     if args.shield is not None:
         print(f"Shield (tau = {args.shield:g}): replaced {r['shield_replaced'].tolist()}, "
               f"no allowed action {r['shield_stuck'].tolist()} agent-steps per RL agent")
-        if args.shield_mode == "joint":
+        if args.shield_mode in ("joint", "joint_crash"):
             print(f"Joint shield ({args.shield_sweeps} sweeps): over tau {r['shield_over'].tolist()} agent-steps per RL "
                   f"agent, {r['shield_unconverged']} env-steps unconverged")
-    if args.shield_crash:
+    if joint_crash:
+        print(f"Coordinated crash shield ({args.shield_sweeps} sweeps): {r['shield_crash_proposed'].tolist()} "
+              f"proposals would have crashed the agent, {r['shield_crash_final'].tolist()} applied actions did, "
+              f"{r['shield_unavoidable'].tolist()} visits had no crash-free action, agent-steps per RL agent; "
+              f"{r['shield_unconverged']} env-steps unconverged")
+    elif args.shield_crash:
         print(f"Crash shield: {r['shield_crash_proposed'].tolist()} proposals would have crashed the agent, "
               f"{r['shield_crash_replaced'].tolist()} of them replaced, agent-steps per RL agent")
     if args.feal:

@@ -57,7 +57,11 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
       shield_mode: "unilateral" or "joint" (at most ``shield_sweeps`` sweeps); joint: also "shield_over" [K]
         and "shield_unconverged".
       shield_crash: the crash-aware shield, alone or with ``shield``; also "shield_crash_proposed" [K] and
-        "shield_crash_replaced" [K].  Unilateral: ValueError with ``shield_mode="joint"``."""
+        "shield_crash_replaced" [K].  Unilateral: ValueError with ``shield_mode="joint"``.
+      shield_mode="joint_crash": the coordinated crash-aware shield (``VecGridEnv.crash_shield_joint``: the crash
+        preview inside the joint sweeps); ``shield=None`` is crash-only, a tau adds FeAR; ``shield_crash`` is
+        implied.  The joint mode's counts, "shield_crash_proposed" [K] (the proposal would have crashed the agent),
+        "shield_crash_final" [K] (the applied joint action does) and "shield_unavoidable" [K]."""
     check_shield_args(shield_mode, shield_crash, "evaluate")
     for kw, on in (("fear_regret=True", fear_regret), ("feal=True", feal), ("resp_full=True", resp_full),
                    ("resp_map=True", resp_map), ("resp_footprint=R", resp_footprint is not None)):
@@ -80,7 +84,7 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         lib = _lib.load()
         folds, cells = build_folds(env, "evaluate", resp_matrix, fear_regret, feal, resp_full, resp_map, resp_footprint)
         guard = None
-        if shield is not None or shield_crash:
+        if shield is not None or shield_crash or shield_mode == "joint_crash":
             guard = Shield(env, shield, shield_mode, shield_sweeps, shield_crash, count_crash=True, who="evaluate")
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None

@@ -217,8 +217,8 @@ def fold_results(folds, widths, flat, all_reduce=None) -> dict:
 
 def check_shield_args(shield_mode: str, shield_crash: bool, who: str = "Rollout"):
     """The shield keywords' checks (no device needed)."""
-    if shield_mode not in ("unilateral", "joint"):
-        raise ValueError(f'{who}(shield_mode=...): "unilateral" or "joint"')
+    if shield_mode not in ("unilateral", "joint", "joint_crash"):
+        raise ValueError(f'{who}(shield_mode=...): "unilateral", "joint" or "joint_crash"')
     if shield_crash and shield_mode == "joint":
         raise ValueError(f'{who}(shield_crash=True) with shield_mode="joint": the crash-aware shield is unilateral')
 
@@ -238,29 +238,43 @@ class Shield:
         ``tau=None`` the table is a zero table under tau = 0: only crashing proposals are replaced, by the most
         probable safe action.  An agent moved to a safe action is crash-free only in envs where every other
         agent's action was kept.
+      coordinated crash-aware (``mode="joint_crash"``; ``crash`` is implied): the one call
+        ``env.crash_shield_joint``, the crash preview inside the joint sweeps: every visit previews the agent's nine
+        actions against the actions fixed so far.  ``tau=None`` is crash-only, a float adds FeAR (``table`` is then
+        set); ``crash9`` holds the own-crash sets under the applied joint action, ``flags`` carries bits 4 (the
+        agent crashes in the step) and 5 (its last visit had no crash-free masked action) too.
     ``flags`` holds the last step's [E, K] uint8 flags.  ``totals()``: "shield_replaced" [K] and "shield_stuck"
     [K] (int64 CPU tensors: the agent-steps whose action was replaced, flag bit 0 / that had no allowed action,
     bit 1); joint: also "shield_over" [K] (the applied action's FeAR exceeds tau, bit 2) and
     "shield_unconverged" (env-steps whose last sweep still changed an action, bit 3); ``count_crash``: also
     "shield_crash_proposed" [K] and "shield_crash_replaced" [K] (the agent-steps whose proposed action would
-    have crashed the agent itself / of those, the ones replaced)."""
+    have crashed the agent itself / of those, the ones replaced); joint_crash: the joint mode's four counts,
+    "shield_crash_proposed" [K] (agent k crashes in the step the proposal would have run), "shield_crash_final" [K]
+    (it crashes in the step that was run, bit 4) and "shield_unavoidable" [K] (bit 5)."""
 
     def __init__(self, env, tau: float | None, mode: str = "unilateral", sweeps: int = 2, crash: bool = False,
                  count_crash: bool = False, who: str = "Rollout"):
         check_shield_args(mode, crash, who)
         E, K, dev = env.E, env.K, env.device
         self.tau = None if tau is None else float(tau)
-        self.joint, self.sweeps, self.crash = mode == "joint", int(sweeps), bool(crash)
+        self.joint_crash = mode == "joint_crash"
+        self.joint, self.sweeps = mode == "joint" or self.joint_crash, int(sweeps)
+        self.crash = bool(crash) or self.joint_crash
         # replaced, stuck; joint mode: over tau, unconverged (bit 3 is the same for an env's K entries)
         self.cnt = torch.zeros((4 if self.joint else 2, K), dtype=torch.int64, device=dev)
         # crashing proposals, of those replaced
         self.crash_cnt = torch.zeros((2, K), dtype=torch.int64, device=dev) if crash and count_crash else None
+        if self.joint_crash:  # proposal crashes, final crashes, unavoidable
+            self.crash_cnt = torch.zeros((3, K), dtype=torch.int64, device=dev)
+            self._outcome_prop = torch.empty(E, dtype=torch.int16, device=dev)
+            self._agent_bit = torch.arange(K, dtype=torch.int64, device=dev).unsqueeze(0)
+            self._flag_bit = torch.arange(6, dtype=torch.uint8, device=dev).reshape(6, 1, 1)
         # the crash shield alone: a zero table under tau = 0, so that only the safe mask decides
         self._table = (torch.zeros if tau is None else torch.empty)((E, K, 9), dtype=torch.float64, device=dev)
         self._out = torch.empty((E, K), dtype=torch.int32, device=dev)
         self.flags = torch.zeros((E, K), dtype=torch.uint8, device=dev)
-        self.table = self._table if self.joint else None
-        self.crash9 = None
+        self.table = self._table if self.joint and not (self.joint_crash and tau is None) else None
+        self.crash9 = torch.empty((E, K), dtype=torch.int16, device=dev) if self.joint_crash else None
         if not self.joint:  # the preview's joint action: the random policy's proposals are read from it
             self._joint = torch.empty((E, env.N), dtype=torch.int32, device=dev)
 
@@ -273,6 +287,16 @@ class Shield:
         def count(cnt, bits):
             cnt += (bits if on is None else bits * on).sum(0)
 
+        if self.joint_crash:
+            r = env.crash_shield_joint(actions, None, mask=mask, probs=probs, tau=self.tau, sweeps=self.sweeps,
+                                       out=self._out, flags=self.flags, table=self.table,
+                                       outcome_prop=self._outcome_prop, crash9=self.crash9)
+            bits = ((r["flags"].unsqueeze(0) >> self._flag_bit) & 1).to(torch.int64)  # [6, E, K], one pass
+            per_bit = (bits if on is None else bits * on).sum(1)
+            self.cnt += per_bit[:4]
+            self.crash_cnt[1:] += per_bit[4:]
+            count(self.crash_cnt[0], (self._outcome_prop.to(torch.int64).unsqueeze(1) >> self._agent_bit) & 1)
+            return r["actions"]
         if self.joint:
             out, flags, _ = env.fear_shield_joint(actions, None, mask=mask, probs=probs, tau=self.tau,
                                                   sweeps=self.sweeps, out=self._out, flags=self.flags,
@@ -304,7 +328,10 @@ class Shield:
     def totals(self, all_reduce=None) -> dict:
         """The counts as CPU tensors (several ranks: summed in one integer all-reduce of their own)."""
         out = {}
-        if self.crash_cnt is not None:
+        if self.joint_crash:
+            cc = _summed(self.crash_cnt, all_reduce)
+            out["shield_crash_proposed"], out["shield_crash_final"], out["shield_unavoidable"] = cc[0], cc[1], cc[2]
+        elif self.crash_cnt is not None:
             cc = _summed(self.crash_cnt, all_reduce)
             out["shield_crash_proposed"], out["shield_crash_replaced"] = cc[0], cc[1]
         cnt = _summed(self.cnt, all_reduce)

@@ -263,6 +263,11 @@ class Rollout:
             the [E, K, 9] table of the applied joint action; also "shield_over" [K], "shield_unconverged".
           shield_crash: the crash-aware shield, alone or with ``shield``; ``shield_crash9`` holds the last
             step's [E, K] own-crash sets.  Unilateral: ValueError with ``shield_mode="joint"``.
+          shield_mode="joint_crash": the coordinated crash-aware shield (``env.crash_shield_joint``), the crash
+            preview inside the joint sweeps; ``shield=None`` is crash-only, a tau adds FeAR (``shield_table`` is
+            then set); ``shield_crash`` is implied.  ``shield_flags`` carries bits 4 (crashes in the step) and 5
+            (unavoidable) too, ``shield_crash9`` the own-crash sets under the applied joint action; totals: the
+            joint mode's, "shield_crash_proposed" [K], "shield_crash_final" [K], "shield_unavoidable" [K].
         Eager only: ``capture`` raises ValueError."""
         self.env = env
         self.actors = actors
@@ -345,7 +350,7 @@ class Rollout:
         self.shield = None if shield is None else float(shield)
         self.shield_mode, self.shield_sweeps, self.shield_crash = shield_mode, int(shield_sweeps), bool(shield_crash)
         self._shield = None
-        if self.shield is not None or self.shield_crash:
+        if self.shield is not None or self.shield_crash or shield_mode == "joint_crash":
             self._shield = Shield(env, self.shield, shield_mode, shield_sweeps, self.shield_crash)
 
     check_shield_args = staticmethod(check_shield_args)

@@ -709,6 +709,80 @@ class VecGridEnv:
                        "gw_fear_shield_joint")
         return out, flags, table
 
+    def crash_shield_joint(self, actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None, *,
+                           mask: torch.Tensor | None = None, probs: torch.Tensor | None = None,
+                           tau: float | None = None, agents: int | None = None, sweeps: int = 2,
+                           out: torch.Tensor | None = None, flags: torch.Tensor | None = None,
+                           table: torch.Tensor | None = None, joint: torch.Tensor | None = None,
+                           outcome: torch.Tensor | None = None, outcome_prop: torch.Tensor | None = None,
+                           crash9: torch.Tensor | None = None) -> dict:
+        """The coordinated crash-aware shield (gw_crash_shield_joint): ``step_preview``'s safe masks inside
+        ``fear_shield_joint``'s sweeps, in one call.  The shielded RL agents are visited one after the other
+        (ascending k, at most ``sweeps`` times round or until a sweep changes nothing); a visit previews the agent's
+        nine actions with the real world update against the actions fixed so far, takes the crashing ones out of
+        its mask (unless all crash) and picks as ``fear_shield`` does.  ``tau=None`` is the crash shield alone (a
+        zero table under tau = 0: only an agent that would crash is moved, to its most probable safe action);
+        a float adds FeAR.  -> a dict of tensors (given, or new ones):
+          "actions" [E, K] int32 (``out``; may be ``actions`` itself), "flags" [E, K] uint8: bits 0-3 as
+            ``fear_shield_joint`` (bit 2 only with a tau), bit 4 the agent crashes in the step that applies
+            "actions", bit 5 every masked action of the agent's last visit crashed it (unavoidable);
+          "table" [E, K, 9] float64: ``fear_preview`` of the applied joint action (with a tau, or when ``table``
+            is given; else absent and no FeAR world update runs);
+          "joint" [E, N] int32 (only when given), "outcome" / "outcome_prop" [E] int16: crash bits | restricted
+            bits << 8 of the step that applies "actions" / of the proposal, "crash9" [E, K] int16: the own-crash
+            sets under the applied joint action (``step_preview``'s).
+        actions / scripted as for ``fear_preview`` (None: the draws the step will make); mask, probs, agents as for
+        ``fear_shield``.  Changes no env state; works with ``fear=False``."""
+        E, K, N = self.E, self.K, self.N
+        self._check_crash_shield_args(E, K, N, actions, scripted, sweeps,
+                                      dict(mask=mask, probs=probs, out=out, flags=flags, table=table, joint=joint,
+                                           outcome=outcome, outcome_prop=outcome_prop, crash9=crash9), self.device)
+        rl = self._as_i32(actions, (E, K))
+        sa = self._as_i32(scripted, (E, N - K))
+        use_fear = tau is not None
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
+        out = new((E, K), torch.int32) if out is None else out
+        flags = new((E, K), torch.uint8) if flags is None else flags
+        if table is None and use_fear:
+            table = new((E, K, 9), torch.float64)
+        outcome = new((E,), torch.int16) if outcome is None else outcome
+        outcome_prop = new((E,), torch.int16) if outcome_prop is None else outcome_prop
+        crash9 = new((E, K), torch.int16) if crash9 is None else crash9
+        bits = (1 << K) - 1 if agents is None else int(agents) & 0xFFFFFFFF
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_crash_shield_joint(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), _ptr(probs),
+                                                      int(use_fear), float(tau) if use_fear else 0.0, bits,
+                                                      int(sweeps), _ptr(out), _ptr(flags), _ptr(table), _ptr(joint),
+                                                      _ptr(outcome), _ptr(outcome_prop), _ptr(crash9), self._stream()),
+                       "gw_crash_shield_joint")
+        res = dict(actions=out, flags=flags, outcome=outcome, outcome_prop=outcome_prop, crash9=crash9)
+        if table is not None:
+            res["table"] = table
+        if joint is not None:
+            res["joint"] = joint
+        return res
+
+    @staticmethod
+    def _check_crash_shield_args(E: int, K: int, N: int, actions, scripted, sweeps, bufs: dict, device=None):
+        """The argument checks of ``crash_shield_joint`` (ValueError before the call; no device needed when
+        ``device`` is None): shapes, dtypes, contiguity and the sweep count."""
+        for t, n, name in ((actions, E * K, "actions"), (scripted, E * (N - K), "scripted")):
+            if t is not None and int(np.prod(np.shape(t))) != n:
+                raise ValueError(f"crash_shield_joint({name}=...): need {n} elements, got shape {tuple(np.shape(t))}")
+        if not 1 <= int(sweeps) <= 8:
+            raise ValueError("crash_shield_joint(sweeps=...): 1..8 (GW_SHIELD_MAX_SWEEPS)")
+        want = dict(mask=(torch.int16, E * K), probs=(torch.float32, K * E * 9), out=(torch.int32, E * K),
+                    flags=(torch.uint8, E * K), table=(torch.float64, E * K * 9), joint=(torch.int32, E * N),
+                    outcome=(torch.int16, E), outcome_prop=(torch.int16, E), crash9=(torch.int16, E * K))
+        for name, t in bufs.items():
+            dt, n = want[name]
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or \
+                    (device is not None and t.device != device):
+                raise ValueError(f"crash_shield_joint({name}=...): need a contiguous {dt} tensor of {n} elements"
+                                 + (f" on {device}" if device is not None else ""))
+
     @staticmethod
     def _check_step_preview_args(E: int, K: int, N: int, rl_actions, scripted, mask):
         """The argument checks of ``step_preview`` that need no device: shapes and the mask's dtype."""

@@ -1,0 +1,223 @@
+"""Coordinated crash-aware shield (gw_crash_shield_joint): what can be checked without a GPU.
+
+1. The floors the seeded cases of tests/_crash_shield_joint_ref.py meet on the CPU reference alone (conditions
+   chosen here so that the GPU comparison reaches every kind of visit): envs where the unilateral crash shield
+   leaves two moved RL agents crashing and the coordinated one none, envs with an unavoidable visit, envs
+   unconverged at one sweep and converged at more, and in the FeAR cases visits that replace for FeAR as well as
+   for crashes; the crash-only and the FeAR setting both occur among the cases.
+2. The visit rule (csrc/crash_shield.h, the text the kernel runs) in the stand-alone host program
+   tools/crash_shield_check.cpp, built with AddressSanitizer + UBSan, on crafted visits and a seeded sample against
+   the rule restated here from include/gridenv.h.
+3. Declaration and wiring: the entry point is declared and exported, GW_SPAN_CRASH_SHIELD = 15, a null env gives
+   GW_ERR_ARG before any device use, the kernel is a translation unit of its own that gridenv.hip does not name,
+   "joint_crash" is an accepted shield mode while "joint" with shield_crash=True still raises, and the wrapper's
+   argument checks that need no device."""
+import ctypes as C
+import inspect
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import _crash_shield_joint_ref as CR
+from _fear_shield_ref import pick_one
+from marlnav import _lib
+
+ALL = 0x1FF
+
+
+# ---- 1. the reference floors -----------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", sorted(CR.CASES))
+def test_reference_floors(name):
+    f = CR.floors(name)
+    print(name, f)
+    assert f["both_moved"] >= 1, f   # what sequential visits remove
+    assert f["unavoidable"] >= 1, f
+    assert f["late"] >= 1, f         # needs more than one sweep, and gets there
+    assert f["for_crash"] >= 1, f
+    if CR.CASES[name][2] is not None:
+        assert f["for_fear"] >= 1, f
+    else:
+        assert f["for_fear"] == 0, f  # without FeAR nothing inside the safe mask is ever moved
+
+
+def test_both_settings_occur():
+    taus = [tau for _, _, tau in CR.CASES.values()]
+    assert any(t is None for t in taus) and any(t is not None for t in taus)
+
+
+def test_reference_promises():
+    """The header's promises that need no step, on the reference itself: the bit 3 / 5 / 4 promise, and that
+    one agent at one sweep is the unilateral pick."""
+    for name in sorted(CR.CASES):
+        sc, spawn, rl, scripted, mask, probs, tau = CR.case(name)
+        r = CR.case_ref(name, CR.FLOOR_SWEEPS)
+        conv = (r["flags"][:, :1] & 8) == 0
+        held = conv & ((mask & ALL) != 0) & ((r["flags"] & 32) == 0)
+        assert held.any() and not (r["flags"][held] & 16).any(), name
+        assert np.array_equal((r["outcome"].astype(np.int64)[:, None] >> np.arange(sc.K)[None, :]) & 1,
+                              (r["flags"] >> 4) & 1)
+    name = "level3_fear"
+    sc, spawn, rl, scripted, mask, probs, tau = CR.case(name)
+    uni, _ = CR.case_unilateral(name)
+    for k in range(sc.K):
+        one = CR.crash_ref(sc, spawn, rl, scripted, mask, probs, tau, 1 << k, 1, orc=CR.case_oracle(name))
+        assert np.array_equal(one["actions"][:, k], uni[:, k])
+        others = [j for j in range(sc.K) if j != k]
+        assert np.array_equal(one["actions"][:, others], rl[:, others])
+
+
+# ---- 2. the rule header under sanitizers -----------------------------------------------------------------
+
+def _visit_ref(has_mask, m, c9, cur, use_fear, tau, pr, t):
+    """include/gridenv.h: m' = the safe mask; the pick on (t or nine zeros, cur, m', pr, tau or 0); the
+    unavoidable bit.  -> (action, flags with bit 5)."""
+    mm = (m & ALL) if has_mask else ALL
+    c9 &= ALL
+    safe = (mm & ~c9) or mm
+    a, f = pick_one(np.asarray(t) if use_fear else np.zeros(9), cur, safe, pr, tau if use_fear else 0.0, True)
+    return a, f | (32 if (mm != 0 and (mm & ~c9) == 0) else 0)
+
+
+PR = np.array([0.05, 0.30, 0.10, 0.30, 0.05, 0.05, 0.05, 0.05, 0.05], np.float32)  # tied maxima at 1 and 3
+T0 = [0.0, 0.5, -0.5, 0.25, 0.0, 1.0, -1.0, 0.0, 0.75]
+
+# (has_mask, mask, crash9, cur, use_fear, tau, has_probs) -> (action, flags), worked out by hand from the rule
+CRAFTED = [
+    ((1, 0x1FF, 0x002, 3, 0, 0.0, 1), (3, 0)),      # crash-only, the current action is safe: kept
+    ((1, 0x1FF, 0x008, 3, 0, 0.0, 1), (1, 1)),      # it crashes: the most probable safe action, ties to the lowest
+    ((1, 0x1FF, 0x008, 3, 0, 0.0, 0), (0, 1)),      # ... without probabilities the lowest safe action
+    ((1, 0x1FF, 0x008, 3, 0, -9.0, 1), (1, 1)),     # tau is ignored without FeAR
+    ((1, 0x00A, 0x00A, 3, 0, 0.0, 1), (3, 32)),     # every masked action crashes: kept, unavoidable
+    ((1, 0x00A, 0x1FF, 5, 0, 0.0, 1), (1, 33)),     # ... and the current one is outside the mask: moved into it
+    ((1, 0x000, 0x1FF, 2, 0, 0.0, 1), (2, 0)),      # mask 0: kept, and not unavoidable
+    ((0, 0x000, 0x1FF, 2, 0, 0.0, 1), (2, 32)),     # no mask, all nine crash
+    ((0, 0x123, 0x004, 2, 0, 0.0, 1), (1, 1)),      # no mask: the mask word is not read
+    ((1, 0x1FF, 0x000, 1, 1, 0.0, 1), (2, 1)),      # FeAR: t[1] = 0.5 > 0; 0, 2, 4, 6, 7 are allowed, 2 the most probable
+    ((1, 0x1FF, 0x004, 1, 1, 0.0, 1), (0, 1)),      # ... with 2 crashing: the first of the 0.05 ones
+    ((1, 0x1FF, 0x000, 2, 1, 0.0, 0), (2, 0)),      # FeAR, allowed and safe: kept
+    ((1, 0x1FF, 0x004, 2, 1, 0.0, 0), (6, 1)),      # FeAR, allowed but crashing, no probs: the least FeAR of the safe ones
+    ((1, 0x022, 0x000, 1, 1, 0.0, 1), (1, 2)),      # nothing allowed (t[1], t[5] > 0): stuck on the least-FeAR masked one
+    ((1, 0x022, 0x002, 1, 1, 0.0, 1), (5, 3)),      # ... with 1 crashing only 5 is left
+    ((1, 0x022, 0x022, 5, 1, 0.0, 1), (1, 35)),     # unavoidable and stuck: the least FeAR of the mask
+    ((1, 0x022, 0x022, 1, 1, 0.0, 1), (1, 34)),     # ... which the agent already plays
+    ((1, 0xFFFF, 0xFE01, 0, 0, 0.0, 1), (1, 1)),    # bits above the nine are ignored in both words
+]
+
+
+def test_visit_rule_under_sanitizers(tmp_path):
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "crash_shield_check")
+    src = os.path.join(_lib.REPO_ROOT, "tools", "crash_shield_check.cpp")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{_lib.CSRC}", src, "-o", exe], check=True, capture_output=True, text=True)
+    rng = np.random.default_rng(20262)
+    cases = [c + (T0, PR) for c, _ in CRAFTED]
+    for _ in range(600):
+        t = rng.choice(np.array([-1.0, -0.5, 0.0, 0.0, 0.25, 0.5, 1.0]), 9).tolist()
+        pr = rng.choice(np.array([0.05, 0.1, 0.2, 0.3], np.float32), 9).astype(np.float32)
+        cases.append((int(rng.integers(0, 2)), int(rng.integers(0, 0x200)), int(rng.integers(0, 0x200)),
+                      int(rng.integers(0, 9)), int(rng.integers(0, 2)), float(rng.choice([-0.5, 0.0, 0.5])),
+                      int(rng.integers(0, 2)), t, pr))
+    for m in (0, 1, 0x100, ALL):  # the edges of both words against each other
+        for c9 in (0, 1, 0x100, ALL):
+            cases.append((1, m, c9, 0, 0, 0.0, 1, T0, PR))
+    text = "".join(f"{h} {hex(m)} {hex(c9)} {cur} {uf} {float(tau).hex()} {hp} " + " ".join(float(x).hex() for x in t)
+                   + " " + " ".join(float(x).hex() for x in pr) + "\n" for h, m, c9, cur, uf, tau, hp, t, pr in cases)
+    r = subprocess.run([exe], input=text, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = [tuple(int(x) for x in ln.split()) for ln in r.stdout.splitlines()]
+    assert len(got) == len(cases)
+    for (case, want), g in zip(CRAFTED, got):
+        assert g == want, (case, g, want)
+    seen = set()
+    for (h, m, c9, cur, uf, tau, hp, t, pr), g in zip(cases, got):
+        want = _visit_ref(h, m, c9, cur, uf, tau, pr if hp else None, t)
+        assert g == want, (h, hex(m), hex(c9), cur, uf, tau, hp, g, want)
+        mm = (m & ALL) if h else ALL
+        if mm and not g[1] & 32:
+            assert (mm >> g[0]) & 1 and not (c9 >> g[0]) & 1  # inside the mask and crash-free
+        seen.add((uf, g[1]))
+    # every flag value occurs with FeAR; without it nothing is ever stuck
+    assert {f for uf, f in seen if uf} >= {0, 1, 2, 3, 32, 33, 34, 35}
+    assert {f for uf, f in seen if not uf} == {0, 1, 32, 33}
+
+
+# ---- 3. declaration and wiring ---------------------------------------------------------------------------
+
+def test_entry_point_is_declared_and_exported():
+    lib = C.CDLL(_lib.build())
+    grid = open(os.path.join(_lib.INCLUDE, "gridenv.h")).read()
+    assert re.search(r"^gw_status gw_crash_shield_joint\(void \*env, const int32_t \*rl_actions, const int32_t \*scripted, "
+                     r"const uint16_t \*mask,\s+const float \*probs, int32_t use_fear, double tau, uint32_t agents, "
+                     r"int32_t sweeps,\s+int32_t \*actions_out, uint8_t \*flags, double \*fear_alt, int32_t \*joint,\s+"
+                     r"uint16_t \*outcome, uint16_t \*outcome_prop, uint16_t \*crash9, void \*stream\);", grid, re.M)
+    assert re.search(r"GW_SPAN_CRASH_SHIELD = 15\b", grid) and re.search(r"GW_SPAN_STEP_PREVIEW = 14\b", grid)
+    assert "gw_crash_shield_joint" in _lib.EXPORTS and hasattr(lib, "gw_crash_shield_joint")
+    p = C.c_void_p
+    lib.gw_crash_shield_joint.argtypes = [p, p, p, p, p, C.c_int32, C.c_double, C.c_uint32, C.c_int32] + [p] * 8
+    assert lib.gw_crash_shield_joint(None, None, None, None, None, 0, 0.0, 3, 2, *[None] * 8) == -1  # GW_ERR_ARG
+    # a translation unit of its own; gridenv.hip only calls its launcher
+    assert os.path.join(_lib.CSRC, "crash_shield_joint.hip") in _lib.HIP_SOURCES
+    assert os.path.join(_lib.CSRC, "crash_shield.h") in _lib.SOURCES
+    src = open(os.path.join(_lib.CSRC, "gridenv.hip")).read()
+    assert "launch_crash_shield_joint" in src and "crash_shield_joint_kernel" not in src
+    kern = open(os.path.join(_lib.CSRC, "crash_shield_joint.hip")).read()
+    assert '#include "crash_shield.h"' in kern and "crash_shield::visit(" in kern and "static_assert" in kern
+    assert "asm" not in kern  # plain C++ stores, no inline assembly
+    rule = open(os.path.join(_lib.CSRC, "crash_shield.h")).read()
+    assert "step_preview::safe_mask(" in rule and "fear_shield::pick(" in rule
+
+
+def test_the_mode_is_accepted_and_the_refusal_stays():
+    from marlnav.evaluate import evaluate
+    from marlnav.resp_folds import check_shield_args
+    from marlnav.rollout import Rollout
+    for crash in (False, True):  # implied, so either is fine
+        check_shield_args("joint_crash", crash)
+        Rollout.check_shield_args("joint_crash", crash)
+    with pytest.raises(ValueError, match="the crash-aware shield is unilateral"):
+        check_shield_args("joint", True)
+    with pytest.raises(ValueError, match="shield_crash"):
+        evaluate(None, "level3", episodes=4, shield_mode="joint", shield_crash=True)
+    with pytest.raises(ValueError, match="shield_mode"):
+        check_shield_args("joint_crashes", False)
+    src = open(os.path.join(_lib.REPO_ROOT, "marl-responsible-nav_amd", "customeval.py")).read()
+    assert '"joint_crash"' in src
+    tool = open(os.path.join(_lib.REPO_ROOT, "tools", "bench_eval_shield.py")).read()
+    assert '"joint_crash"' in tool and '"joint0_crash"' in tool
+
+
+def test_wrapper_signature_and_argument_checks():
+    from marlnav.vec_env import VecGridEnv
+    p = inspect.signature(VecGridEnv.crash_shield_joint).parameters
+    assert list(p)[1:] == ["actions", "scripted", "mask", "probs", "tau", "agents", "sweeps", "out", "flags", "table",
+                           "joint", "outcome", "outcome_prop", "crash9"]
+    assert all(p[n].kind is inspect.Parameter.KEYWORD_ONLY for n in list(p)[3:])
+    assert p["tau"].default is None and p["sweeps"].default == 2
+    chk = VecGridEnv._check_crash_shield_args
+    E, K, N = 5, 2, 4
+    chk(E, K, N, None, None, 2, {})
+    chk(E, K, N, np.zeros((E, K), np.int32), np.zeros((E, N - K), np.int32), 8,
+        dict(mask=torch.zeros((E, K), dtype=torch.int16), outcome=torch.zeros(E, dtype=torch.int16)))
+    with pytest.raises(ValueError, match="actions"):
+        chk(E, K, N, np.zeros((E, K + 1), np.int32), None, 2, {})
+    with pytest.raises(ValueError, match="scripted"):
+        chk(E, K, N, None, np.zeros((E, N), np.int32), 2, {})
+    for sweeps in (0, 9):
+        with pytest.raises(ValueError, match="sweeps"):
+            chk(E, K, N, None, None, sweeps, {})
+    bad = dict(mask=torch.zeros((E, K), dtype=torch.int32), probs=torch.zeros((K, E, 8)),
+               out=torch.zeros((E, K), dtype=torch.int64), flags=torch.zeros((E, K), dtype=torch.int8),
+               table=torch.zeros((E, K, 9)), joint=torch.zeros((E, K), dtype=torch.int32),
+               outcome=torch.zeros((E, 2), dtype=torch.int16), outcome_prop=torch.zeros(E, dtype=torch.uint8),
+               crash9=torch.zeros((K, E), dtype=torch.int16).t())
+    for name, t in bad.items():
+        with pytest.raises(ValueError, match=name):
+            chk(E, K, N, None, None, 2, {name: t})

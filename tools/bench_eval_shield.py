@@ -15,7 +15,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "marl-responsible-nav_amd")]
 import torch  # noqa: E402
 
 SETTINGS = (("plain", {}), ("shield0", dict(shield=0.0)), ("shield0_crash", dict(shield=0.0, shield_crash=True)),
-            ("crash", dict(shield_crash=True)), ("joint0", dict(shield=0.0, shield_mode="joint")))
+            ("crash", dict(shield_crash=True)), ("joint0", dict(shield=0.0, shield_mode="joint")),
+            ("joint_crash", dict(shield_mode="joint_crash")), ("joint0_crash", dict(shield=0.0, shield_mode="joint_crash")))
 
 
 def main(argv=None):
