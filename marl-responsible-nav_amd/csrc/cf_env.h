@@ -539,28 +539,12 @@ struct StepPreviewArgs {
 hipError_t launch_step_preview(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
                                const StepPreviewArgs &a);
 
-// gw_fear_shield_joint's arguments beside the env's (include/gridenv.h): mask [E][K] or null, probs [K][E][9] or
-// null, agents / sweeps already checked, actions_out [E][K], flags [E][K] / table [E][K][9] / joint [E][N] or null
-struct ShieldJointArgs {
-    const uint16_t *mask;
-    const float *probs;
-    double tau;
-    uint32_t agents;
-    int sweeps;
-    int32_t *actions_out;
-    uint8_t *flags;
-    double *table;
-    int32_t *joint;
-};
-
-// fear_shield_joint_kernel<N> (fear_shield_joint.hip, gw_fear_shield_joint) over p's env range on s, through
-// gwprof::launch, from the record in p.fwork
-hipError_t launch_fear_shield_joint(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
-                                    const ShieldJointArgs &a);
-
-// gw_crash_shield_joint's arguments beside the env's (include/gridenv.h): ShieldJointArgs' plus use_fear and the
-// outputs outcome [E] / outcome_prop [E] / crash9 [E][K] or null
-struct CrashShieldArgs {
+// The arguments of the two joint shields beside the env's (include/gridenv.h; the kernels' one body:
+// shield_joint_core.h): mask [E][K] or null, probs [K][E][9] or null, agents / sweeps already checked,
+// actions_out [E][K], flags [E][K] / table [E][K][9] / joint [E][N] or null.  gw_crash_shield_joint alone reads
+// use_fear and the outputs outcome [E] / outcome_prop [E] / crash9 [E][K] or null; gw_fear_shield_joint passes
+// use_fear = 1 and null for the three
+struct JointShieldArgs {
     const uint16_t *mask;
     const float *probs;
     int use_fear;
@@ -576,10 +560,13 @@ struct CrashShieldArgs {
     uint16_t *crash9;
 };
 
-// crash_shield_joint_kernel<N> (crash_shield_joint.hip, gw_crash_shield_joint) over p's env range on s, through
-// gwprof::launch, from the record in p.fwork
+// fear_shield_joint_kernel<N> (fear_shield_joint.hip, gw_fear_shield_joint) and crash_shield_joint_kernel<N>
+// (crash_shield_joint.hip, gw_crash_shield_joint) over p's env range on s, through gwprof::launch, from the
+// record in p.fwork
+hipError_t launch_fear_shield_joint(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
+                                    const JointShieldArgs &a);
 hipError_t launch_crash_shield_joint(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
-                                     const CrashShieldArgs &a);
+                                     const JointShieldArgs &a);
 
 // fear_alt_kernel<N> (fear_cf.hip; gw_set_fear_alt, and gw_fear_preview on the preview's record) over p's env
 // range on s, through gwprof::launch: table [E][K][9]

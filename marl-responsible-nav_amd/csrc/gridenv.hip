@@ -1949,6 +1949,43 @@ gw_status launch_cf(Env *env, int kind, const gw::Params &p0, F &&launch) {
     return GW_OK;
 }
 
+// a preview entry's record buffer (env->preview_rec, which gw_fear_preview and the two joint shields share, or
+// gw_step_preview's own), allocated by the first call
+gw_status ensure_preview_rec(Env *env, hipStream_t s, const char *who, uint4 **rec) {
+    if (*rec) return GW_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;  // hipMalloc is not allowed while the stream captures
+    HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return fail(GW_ERR_STATE, (std::string(who) + ": the first call allocates the record buffer and cannot run "
+                                   "while the stream is capturing; call it once before the capture").c_str());
+    return dalloc(env, rec, (size_t)env->E * (env->N <= 4 ? 1 : 2));
+}
+
+// What the preview entries (`who`: gw_step_preview, gw_fear_preview, gw_fear_shield_joint, gw_crash_shield_joint)
+// do after their own argument checks, as one span of `kind`: the record of the step that gw_step(rl, scripted)
+// would run next into *buf (the record builder, fear_preview.hip; its joint action and MdRs into actions / mdr,
+// [E][N] or null), then second(grid, block, dyn, q), the entry's own kernel on that record (a code object of
+// its own).  The env's state as the next gw_step will read it: every path orders the last world update before
+// the caller's later work on its stream.  No step output, no descriptor, no pipeline state is touched
+template <typename F>
+gw_status preview_call(Env *env, const char *who, uint4 **buf, int kind, const int32_t *rl, const int32_t *scripted,
+                       int32_t *actions, int32_t *mdr, hipStream_t s, F &&second) {
+    if (!env->initialized) return fail(GW_ERR_STATE, std::string(who) + " before gw_reset");
+    GW_TRY(ensure_preview_rec(env, s, who, buf));
+    gw::Params p = make_params(env);
+    p.rl = rl;
+    p.scripted = scripted;
+    p.fwork = *buf;
+    hipError_t rec = hipSuccess;
+    GW_TRY(launch_cf(env, kind, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+        rec = gw::launch_preview_rec(env->N, s, q, actions, mdr);
+        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
+        rec = second(grid, block, dyn, q);
+    }));
+    HIP_TRY(rec);
+    return GW_OK;
+}
+
 hipError_t launch_reset(const Env *env, const gw::Params &p, hipStream_t s) {
     return gw::with_agents(env->N, hipErrorInvalidValue, [&](auto n) {
         gw_launch((gw::reset_kernel<decltype(n)::value>), dim3((unsigned)ceil_div(env->E, 256)), dim3(256), 0, s, p);
@@ -2935,44 +2972,19 @@ gw_status gw_set_fear_full(void *handle, double *resp_full, uint16_t *resp_valid
     return GW_OK;
 }
 
-// the record buffer gw_fear_preview and gw_fear_shield_joint share (env->preview_rec, the default) or
-// gw_step_preview's own, allocated by the first call
-static gw_status ensure_preview_rec(Env *env, hipStream_t s, const char *who, uint4 **rec = nullptr) {
-    if (!rec) rec = &env->preview_rec;
-    if (*rec) return GW_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;  // hipMalloc is not allowed while the stream captures
-    HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return fail(GW_ERR_STATE, (std::string(who) + ": the first call allocates the record buffer and cannot run "
-                                   "while the stream is capturing; call it once before the capture").c_str());
-    return dalloc(env, rec, (size_t)env->E * (env->N <= 4 ? 1 : 2));
-}
-
 gw_status gw_step_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
                           uint16_t *outcome, double *reward_alt, uint16_t *crash9, uint16_t *safe_mask,
                           int32_t *actions, void *stream) {
     Env *env = static_cast<Env *>(handle);
     if (!env) return fail(GW_ERR_ARG, "gw_step_preview: null env");
     if (!outcome) return fail(GW_ERR_ARG, "gw_step_preview: null outcome");
-    if (!env->initialized) return fail(GW_ERR_STATE, "gw_step_preview before gw_reset");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    GW_TRY(ensure_preview_rec(env, s, "gw_step_preview", &env->step_preview_rec));
-    // as gw_fear_preview: the env's state as the next gw_step will read it, nothing of the env written
-    gw::Params p = make_params(env);
-    p.rl = rl_actions;
-    p.scripted = scripted;
-    p.fwork = env->step_preview_rec;
     const gw::StepPreviewArgs a{mask, outcome, reward_alt, crash9, safe_mask};
-    hipError_t rec = hipSuccess;
-    GW_TRY(launch_cf(env, GW_SPAN_STEP_PREVIEW, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
-        // the record of the step's joint action (fear_preview.hip), then the K x 9 real world updates on it
-        // (step_preview.hip, its own code object): both launches are the one span
-        rec = gw::launch_preview_rec(env->N, s, q, actions, nullptr);
-        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
-        rec = gw::launch_step_preview(env->N, grid, block, dyn, s, q, a);
-    }));
-    HIP_TRY(rec);
-    return GW_OK;
+    // the K x 9 real world updates on the record (step_preview.hip); a record buffer of its own
+    return preview_call(env, "gw_step_preview", &env->step_preview_rec, GW_SPAN_STEP_PREVIEW, rl_actions, scripted,
+                        actions, nullptr, s, [&](dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+                            return gw::launch_step_preview(env->N, grid, block, dyn, s, q, a);
+                        });
 }
 
 gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,
@@ -2980,25 +2992,12 @@ gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t
     Env *env = static_cast<Env *>(handle);
     if (!env) return fail(GW_ERR_ARG, "gw_fear_preview: null env");
     if (!fear_alt) return fail(GW_ERR_ARG, "gw_fear_preview: null table");
-    if (!env->initialized) return fail(GW_ERR_STATE, "gw_fear_preview before gw_reset");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    GW_TRY(ensure_preview_rec(env, s, "gw_fear_preview"));
-    // the env's state as the next gw_step will read it: every path orders the last world update before the
-    // caller's later work on its stream.  No step output, no descriptor, no pipeline state is touched
-    gw::Params p = make_params(env);
-    p.rl = rl_actions;
-    p.scripted = scripted;
-    p.fwork = env->preview_rec;
-    hipError_t rec = hipSuccess;
-    GW_TRY(launch_cf(env, GW_SPAN_FEAR_PREVIEW, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
-        // the record builder (fear_preview.hip, its own code object), then the step's own table kernel
-        // (fear_cf.hip) on that record: both launches are the one span
-        rec = gw::launch_preview_rec(env->N, s, q, actions, mdr);
-        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
-        (void)gw::launch_fear_alt(env->N, grid, block, dyn, s, q, fear_alt);
-    }));
-    HIP_TRY(rec);
-    return GW_OK;
+    // the step's own table kernel (fear_cf.hip) on the record
+    return preview_call(env, "gw_fear_preview", &env->preview_rec, GW_SPAN_FEAR_PREVIEW, rl_actions, scripted,
+                        actions, mdr, s, [&](dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+                            return gw::launch_fear_alt(env->N, grid, block, dyn, s, q, fear_alt);
+                        });
 }
 
 gw_status gw_fear_shield_joint(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
@@ -3009,25 +3008,14 @@ gw_status gw_fear_shield_joint(void *handle, const int32_t *rl_actions, const in
     if (!actions_out) return fail(GW_ERR_ARG, "gw_fear_shield_joint: null actions_out");
     if (sweeps < 1 || sweeps > GW_SHIELD_MAX_SWEEPS)
         return fail(GW_ERR_ARG, "gw_fear_shield_joint: sweeps outside 1..GW_SHIELD_MAX_SWEEPS");
-    if (!env->initialized) return fail(GW_ERR_STATE, "gw_fear_shield_joint before gw_reset");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    GW_TRY(ensure_preview_rec(env, s, "gw_fear_shield_joint"));
-    // as gw_fear_preview: the env's state as the next gw_step will read it, nothing of the env written
-    gw::Params p = make_params(env);
-    p.rl = rl_actions;
-    p.scripted = scripted;
-    p.fwork = env->preview_rec;
-    const gw::ShieldJointArgs a{mask, probs, tau, agents, sweeps, actions_out, flags, fear_alt, joint};
-    hipError_t rec = hipSuccess;
-    GW_TRY(launch_cf(env, GW_SPAN_FEAR_SHIELD, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
-        // the record of the proposed joint action, then the sweeps and the final table on it (fear_shield_joint.hip,
-        // its own code object): both launches are the one span
-        rec = gw::launch_preview_rec(env->N, s, q, nullptr, nullptr);
-        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
-        rec = gw::launch_fear_shield_joint(env->N, grid, block, dyn, s, q, a);
-    }));
-    HIP_TRY(rec);
-    return GW_OK;
+    const gw::JointShieldArgs a{mask, probs, 1, tau, agents, sweeps, actions_out, flags, fear_alt, joint,
+                                nullptr, nullptr, nullptr};
+    // the sweeps and the final table on the record of the proposed joint action (fear_shield_joint.hip)
+    return preview_call(env, "gw_fear_shield_joint", &env->preview_rec, GW_SPAN_FEAR_SHIELD, rl_actions, scripted,
+                        nullptr, nullptr, s, [&](dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+                            return gw::launch_fear_shield_joint(env->N, grid, block, dyn, s, q, a);
+                        });
 }
 
 gw_status gw_crash_shield_joint(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
@@ -3039,26 +3027,14 @@ gw_status gw_crash_shield_joint(void *handle, const int32_t *rl_actions, const i
     if (!actions_out) return fail(GW_ERR_ARG, "gw_crash_shield_joint: null actions_out");
     if (sweeps < 1 || sweeps > GW_SHIELD_MAX_SWEEPS)
         return fail(GW_ERR_ARG, "gw_crash_shield_joint: sweeps outside 1..GW_SHIELD_MAX_SWEEPS");
-    if (!env->initialized) return fail(GW_ERR_STATE, "gw_crash_shield_joint before gw_reset");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    GW_TRY(ensure_preview_rec(env, s, "gw_crash_shield_joint"));
-    // as gw_fear_preview: the env's state as the next gw_step will read it, nothing of the env written
-    gw::Params p = make_params(env);
-    p.rl = rl_actions;
-    p.scripted = scripted;
-    p.fwork = env->preview_rec;
-    const gw::CrashShieldArgs a{mask, probs, use_fear != 0, use_fear ? tau : 0.0, agents, sweeps, actions_out,
+    const gw::JointShieldArgs a{mask, probs, use_fear != 0, use_fear ? tau : 0.0, agents, sweeps, actions_out,
                                 flags, fear_alt, joint, outcome, outcome_prop, crash9};
-    hipError_t rec = hipSuccess;
-    GW_TRY(launch_cf(env, GW_SPAN_CRASH_SHIELD, p, [&](auto, dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
-        // the record of the proposed joint action, then the sweeps, the final outcome and table on it
-        // (crash_shield_joint.hip, its own code object): both launches are the one span
-        rec = gw::launch_preview_rec(env->N, s, q, nullptr, nullptr);
-        if (rec != hipSuccess || hipPeekAtLastError() != hipSuccess) return;
-        rec = gw::launch_crash_shield_joint(env->N, grid, block, dyn, s, q, a);
-    }));
-    HIP_TRY(rec);
-    return GW_OK;
+    // the sweeps, the final outcome and table on the record of the proposed joint action (crash_shield_joint.hip)
+    return preview_call(env, "gw_crash_shield_joint", &env->preview_rec, GW_SPAN_CRASH_SHIELD, rl_actions, scripted,
+                        nullptr, nullptr, s, [&](dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+                            return gw::launch_crash_shield_joint(env->N, grid, block, dyn, s, q, a);
+                        });
 }
 
 gw_status gw_obs_desc_copy(void *handle, uint32_t *dst, void *stream) {

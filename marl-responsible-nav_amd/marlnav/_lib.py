@@ -44,7 +44,7 @@ SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.jo
                                    os.path.join(CSRC, "grad_core.h"), os.path.join(CSRC, "desc_rows.h"),
                                    os.path.join(CSRC, "resp_map.h"), os.path.join(CSRC, "fear_alt_core.h"),
                                    os.path.join(CSRC, "resp_footprint.h"), os.path.join(CSRC, "step_preview.h"),
-                                   os.path.join(CSRC, "crash_shield.h")]
+                                   os.path.join(CSRC, "crash_shield.h"), os.path.join(CSRC, "shield_joint_core.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

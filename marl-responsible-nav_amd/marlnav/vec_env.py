@@ -37,6 +37,7 @@ Layouts (device tensors, owned by the env and overwritten by the next call):
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import itertools
 import os
 from dataclasses import dataclass
@@ -628,13 +629,9 @@ class VecGridEnv:
         E, K, N = self.E, self.K, self.N
         rl = self._as_i32(rl_actions, (E, K))
         sa = self._as_i32(scripted, (E, N - K))
-        if out is None:
-            out = torch.empty((E, K, 9), dtype=torch.float64, device=self.device)
-        for t, dt, n, name in ((out, torch.float64, E * K * 9, "out"), (actions, torch.int32, E * N, "actions"),
-                               (mdr, torch.int32, E * N, "mdr")):
-            if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device):
-                raise ValueError(f"fear_preview({name}=...): need a contiguous {dt} tensor of {n} elements on "
-                                 f"{self.device}")
+        out = self._empty((E, K, 9), torch.float64) if out is None else out
+        self._check_bufs("fear_preview", dict(out=out, actions=actions, mdr=mdr),
+                         self._want_bufs("fear_preview", E, K, N), self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gw_fear_preview(self.handle, _ptr(rl), _ptr(sa), _ptr(out), _ptr(actions), _ptr(mdr),
                                                 self._stream()), "gw_fear_preview")
@@ -653,17 +650,11 @@ class VecGridEnv:
         agents keep their proposed actions (include/rollout_ops.h)."""
         E, K = self.E, self.K
         act = self._as_i32(actions, (E, K))
-        if out is None:
-            out = torch.empty((E, K), dtype=torch.int32, device=self.device)
-        if flags is None:
-            flags = torch.empty((E, K), dtype=torch.uint8, device=self.device)
-        for t, dt, n, name in ((table, torch.float64, E * K * 9, "table"), (mask, torch.int16, E * K, "mask"),
-                               (probs, torch.float32, K * E * 9, "probs"), (out, torch.int32, E * K, "out"),
-                               (flags, torch.uint8, E * K, "flags")):
-            if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device):
-                raise ValueError(f"fear_shield({name}=...): need a contiguous {dt} tensor of {n} elements on "
-                                 f"{self.device}")
-        bits = (1 << K) - 1 if agents is None else int(agents) & 0xFFFFFFFF
+        out = self._empty((E, K), torch.int32) if out is None else out
+        flags = self._empty((E, K), torch.uint8) if flags is None else flags
+        self._check_bufs("fear_shield", dict(table=table, mask=mask, probs=probs, out=out, flags=flags),
+                         self._want_bufs("fear_shield", E, K, self.N), self.device)
+        bits = self._agent_bits(K, agents)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gw_fear_shield(_ptr(table), _ptr(act), _ptr(mask), _ptr(probs), E, K, float(tau), bits,
                                                _ptr(out), _ptr(flags), self._stream()), "gw_fear_shield")
@@ -687,21 +678,13 @@ class VecGridEnv:
         E, K, N = self.E, self.K, self.N
         rl = self._as_i32(rl_actions, (E, K))
         sa = self._as_i32(scripted, (E, N - K))
-        if not 1 <= int(sweeps) <= 8:
-            raise ValueError("fear_shield_joint(sweeps=...): 1..8 (GW_SHIELD_MAX_SWEEPS)")
-        if out is None:
-            out = torch.empty((E, K), dtype=torch.int32, device=self.device)
-        if flags is None:
-            flags = torch.empty((E, K), dtype=torch.uint8, device=self.device)
-        if table is None:
-            table = torch.empty((E, K, 9), dtype=torch.float64, device=self.device)
-        for t, dt, n, name in ((table, torch.float64, E * K * 9, "table"), (mask, torch.int16, E * K, "mask"),
-                               (probs, torch.float32, K * E * 9, "probs"), (out, torch.int32, E * K, "out"),
-                               (flags, torch.uint8, E * K, "flags"), (joint, torch.int32, E * N, "joint")):
-            if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != self.device):
-                raise ValueError(f"fear_shield_joint({name}=...): need a contiguous {dt} tensor of {n} elements on "
-                                 f"{self.device}")
-        bits = (1 << K) - 1 if agents is None else int(agents) & 0xFFFFFFFF
+        self._check_sweeps("fear_shield_joint", sweeps)
+        out = self._empty((E, K), torch.int32) if out is None else out
+        flags = self._empty((E, K), torch.uint8) if flags is None else flags
+        table = self._empty((E, K, 9), torch.float64) if table is None else table
+        self._check_bufs("fear_shield_joint", dict(table=table, mask=mask, probs=probs, out=out, flags=flags, joint=joint),
+                         self._want_bufs("fear_shield_joint", E, K, N), self.device)
+        bits = self._agent_bits(K, agents)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gw_fear_shield_joint(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), _ptr(probs),
                                                      float(tau), bits, int(sweeps), _ptr(out), _ptr(flags),
@@ -740,15 +723,13 @@ class VecGridEnv:
         rl = self._as_i32(actions, (E, K))
         sa = self._as_i32(scripted, (E, N - K))
         use_fear = tau is not None
-        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
-        out = new((E, K), torch.int32) if out is None else out
-        flags = new((E, K), torch.uint8) if flags is None else flags
-        if table is None and use_fear:
-            table = new((E, K, 9), torch.float64)
-        outcome = new((E,), torch.int16) if outcome is None else outcome
-        outcome_prop = new((E,), torch.int16) if outcome_prop is None else outcome_prop
-        crash9 = new((E, K), torch.int16) if crash9 is None else crash9
-        bits = (1 << K) - 1 if agents is None else int(agents) & 0xFFFFFFFF
+        out = self._empty((E, K), torch.int32) if out is None else out
+        flags = self._empty((E, K), torch.uint8) if flags is None else flags
+        table = self._empty((E, K, 9), torch.float64) if table is None and use_fear else table
+        outcome = self._empty((E,), torch.int16) if outcome is None else outcome
+        outcome_prop = self._empty((E,), torch.int16) if outcome_prop is None else outcome_prop
+        crash9 = self._empty((E, K), torch.int16) if crash9 is None else crash9
+        bits = self._agent_bits(K, agents)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gw_crash_shield_joint(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), _ptr(probs),
                                                       int(use_fear), float(tau) if use_fear else 0.0, bits,
@@ -756,44 +737,62 @@ class VecGridEnv:
                                                       _ptr(outcome), _ptr(outcome_prop), _ptr(crash9), self._stream()),
                        "gw_crash_shield_joint")
         res = dict(actions=out, flags=flags, outcome=outcome, outcome_prop=outcome_prop, crash9=crash9)
-        if table is not None:
-            res["table"] = table
-        if joint is not None:
-            res["joint"] = joint
-        return res
+        return {**res, **{n: t for n, t in (("table", table), ("joint", joint)) if t is not None}}
+
+    def _empty(self, shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=self.device)
+
+    @staticmethod
+    def _agent_bits(K: int, agents):  # the shields' ``agents`` as the library's bitmask (None: all K RL agents)
+        return (1 << K) - 1 if agents is None else int(agents) & 0xFFFFFFFF
+
+    @staticmethod
+    def _check_sweeps(who: str, sweeps):
+        if not 1 <= int(sweeps) <= 8:
+            raise ValueError(f"{who}(sweeps=...): 1..8 (GW_SHIELD_MAX_SWEEPS)")
+
+    @staticmethod
+    def _check_counts(who: str, **given):  # argument name = (array-like or None, the elements it must hold)
+        for name, (t, n) in given.items():
+            if t is not None and int(np.prod(np.shape(t))) != n:
+                raise ValueError(f"{who}({name}=...): need {n} elements, got shape {tuple(np.shape(t))}")
+
+    @staticmethod
+    @functools.lru_cache(maxsize=None)  # a per-step call path: the table is built once per method and shape
+    def _want_bufs(who: str, E: int, K: int, N: int) -> dict:
+        """(dtype, elements) of the buffers that method ``who`` takes, by argument name (_check_bufs' ``want``)."""
+        if who == "fear_preview":
+            return dict(out=(torch.float64, E * K * 9), actions=(torch.int32, E * N), mdr=(torch.int32, E * N))
+        return dict(mask=(torch.int16, E * K), probs=(torch.float32, K * E * 9), out=(torch.int32, E * K),
+                    flags=(torch.uint8, E * K), table=(torch.float64, E * K * 9), joint=(torch.int32, E * N),
+                    outcome=(torch.int16, E), outcome_prop=(torch.int16, E), crash9=(torch.int16, E * K))
+
+    @staticmethod
+    def _check_bufs(who: str, bufs: dict, want: dict, device=None, note: str = ""):
+        """The buffer check of the preview and shield methods (``who``: the method's name): every tensor of ``bufs``
+        (argument name -> tensor; None: not given) has the dtype and the element count of ``want[name]``, is
+        contiguous and, if a ``device`` is given, lies on it; else ValueError naming the method and the argument."""
+        for name, t in bufs.items():
+            dt, n = want[name]
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.numel() == n
+                                      and t.is_contiguous() and (device is None or t.device == device)):
+                raise ValueError(f"{who}({name}=...): need a contiguous {dt} tensor of {n} elements"
+                                 + (f" on {device}" if device is not None else "") + note)
 
     @staticmethod
     def _check_crash_shield_args(E: int, K: int, N: int, actions, scripted, sweeps, bufs: dict, device=None):
         """The argument checks of ``crash_shield_joint`` (ValueError before the call; no device needed when
         ``device`` is None): shapes, dtypes, contiguity and the sweep count."""
-        for t, n, name in ((actions, E * K, "actions"), (scripted, E * (N - K), "scripted")):
-            if t is not None and int(np.prod(np.shape(t))) != n:
-                raise ValueError(f"crash_shield_joint({name}=...): need {n} elements, got shape {tuple(np.shape(t))}")
-        if not 1 <= int(sweeps) <= 8:
-            raise ValueError("crash_shield_joint(sweeps=...): 1..8 (GW_SHIELD_MAX_SWEEPS)")
-        want = dict(mask=(torch.int16, E * K), probs=(torch.float32, K * E * 9), out=(torch.int32, E * K),
-                    flags=(torch.uint8, E * K), table=(torch.float64, E * K * 9), joint=(torch.int32, E * N),
-                    outcome=(torch.int16, E), outcome_prop=(torch.int16, E), crash9=(torch.int16, E * K))
-        for name, t in bufs.items():
-            dt, n = want[name]
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or \
-                    (device is not None and t.device != device):
-                raise ValueError(f"crash_shield_joint({name}=...): need a contiguous {dt} tensor of {n} elements"
-                                 + (f" on {device}" if device is not None else ""))
+        VecGridEnv._check_counts("crash_shield_joint", actions=(actions, E * K), scripted=(scripted, E * (N - K)))
+        VecGridEnv._check_sweeps("crash_shield_joint", sweeps)
+        VecGridEnv._check_bufs("crash_shield_joint", bufs, VecGridEnv._want_bufs("crash_shield_joint", E, K, N), device)
 
     @staticmethod
     def _check_step_preview_args(E: int, K: int, N: int, rl_actions, scripted, mask):
         """The argument checks of ``step_preview`` that need no device: shapes and the mask's dtype."""
-        for t, n, name in ((rl_actions, E * K, "rl_actions"), (scripted, E * (N - K), "scripted")):
-            if t is not None and int(np.prod(np.shape(t))) != n:
-                raise ValueError(f"step_preview({name}=...): need {n} elements, got shape {tuple(np.shape(t))}")
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int16 or mask.numel() != E * K \
-                    or not mask.is_contiguous():
-                raise ValueError(f"step_preview(mask=...): need a contiguous torch.int16 tensor of {E * K} elements "
-                                 "(the 9-bit action masks, as StepResult.mask)")
+        VecGridEnv._check_counts("step_preview", rl_actions=(rl_actions, E * K), scripted=(scripted, E * (N - K)))
+        VecGridEnv._check_bufs("step_preview", dict(mask=mask), dict(mask=(torch.int16, E * K)),
+                               note=" (the 9-bit action masks, as StepResult.mask)")
 
     def step_preview(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
                      mask: torch.Tensor | None = None, reward: bool = True) -> dict:

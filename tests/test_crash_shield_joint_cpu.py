@@ -168,7 +168,11 @@ def test_entry_point_is_declared_and_exported():
     assert os.path.join(_lib.CSRC, "crash_shield.h") in _lib.SOURCES
     src = open(os.path.join(_lib.CSRC, "gridenv.hip")).read()
     assert "launch_crash_shield_joint" in src and "crash_shield_joint_kernel" not in src
+    # the kernel's text: its wrapper and the body it shares with fear_shield_joint_kernel
     kern = open(os.path.join(_lib.CSRC, "crash_shield_joint.hip")).read()
+    assert '#include "shield_joint_core.h"' in kern and "shield_joint_body<N, true>(" in kern
+    assert os.path.join(_lib.CSRC, "shield_joint_core.h") in _lib.SOURCES
+    kern += open(os.path.join(_lib.CSRC, "shield_joint_core.h")).read()
     assert '#include "crash_shield.h"' in kern and "crash_shield::visit(" in kern and "static_assert" in kern
     assert "asm" not in kern  # plain C++ stores, no inline assembly
     rule = open(os.path.join(_lib.CSRC, "crash_shield.h")).read()
@@ -221,3 +225,33 @@ def test_wrapper_signature_and_argument_checks():
     for name, t in bad.items():
         with pytest.raises(ValueError, match=name):
             chk(E, K, N, None, None, 2, {name: t})
+
+
+def test_check_bufs_names_the_method_and_the_argument():
+    """VecGridEnv._check_bufs, the one buffer check of fear_preview, fear_shield, fear_shield_joint and
+    crash_shield_joint, with each method's own table: a wrong dtype, a wrong size and a non-contiguous tensor each
+    raise ValueError naming the method and the argument; the right tensor and None pass.  No device."""
+    from marlnav.vec_env import VecGridEnv
+    E, K, N = 5, 2, 4
+    other = {torch.float64: torch.float32, torch.float32: torch.float64, torch.int32: torch.int16,
+             torch.int16: torch.int32, torch.uint8: torch.int8}
+    names = dict(fear_preview=["out", "actions", "mdr"], fear_shield=["table", "mask", "probs", "out", "flags"],
+                 fear_shield_joint=["table", "mask", "probs", "out", "flags", "joint"],
+                 crash_shield_joint=["mask", "probs", "out", "flags", "table", "joint", "outcome", "outcome_prop",
+                                     "crash9"])
+    for who, args in names.items():
+        want = VecGridEnv._want_bufs(who, E, K, N)
+        for name in args:
+            dt, n = want[name]
+            assert n > 1
+            VecGridEnv._check_bufs(who, {name: torch.zeros(n, dtype=dt)}, want)
+            VecGridEnv._check_bufs(who, {name: None}, want)
+            bad = dict(dtype=torch.zeros(n, dtype=other[dt]), size=torch.zeros(n + 1, dtype=dt),
+                       strided=torch.zeros(2 * n, dtype=dt)[::2])
+            assert bad["strided"].numel() == n and not bad["strided"].is_contiguous()
+            for t in bad.values():
+                with pytest.raises(ValueError, match=rf"^{who}\({name}=\.\.\.\): need a contiguous {dt} tensor of {n} "):
+                    VecGridEnv._check_bufs(who, {name: t}, want)
+    with pytest.raises(ValueError, match=r"elements on cpu$"):  # with a device the text says where
+        VecGridEnv._check_bufs("fear_preview", dict(mdr=torch.zeros(3, dtype=torch.int32)),
+                               VecGridEnv._want_bufs("fear_preview", E, K, N), torch.device("cpu"))
