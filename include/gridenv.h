@@ -166,7 +166,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * GW_SPAN_FEAR_PREVIEW the two launches of gw_fear_preview (preview_rec_kernel, fear_alt_kernel),
  * GW_SPAN_FEAR_SHIELD the two launches of gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel),
  * GW_SPAN_STEP_PREVIEW the two launches of gw_step_preview (preview_rec_kernel, step_preview_kernel),
- * GW_SPAN_CRASH_SHIELD the two launches of gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel).
+ * GW_SPAN_CRASH_SHIELD the two launches of gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel),
+ * GW_SPAN_STEP_LOOKAHEAD the two launches of gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -177,7 +178,8 @@ enum {
     GW_SPAN_FEAR_ALT = 9, GW_SPAN_FEAL = 10, GW_SPAN_FEAR_FULL = 11, GW_SPAN_FEAR_PREVIEW = 12,
     GW_SPAN_FEAR_SHIELD = 13 /* the two launches of one gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel) */,
     GW_SPAN_STEP_PREVIEW = 14 /* the two launches of one gw_step_preview (preview_rec_kernel, step_preview_kernel) */,
-    GW_SPAN_CRASH_SHIELD = 15 /* the two launches of one gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel) */
+    GW_SPAN_CRASH_SHIELD = 15 /* the two launches of one gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel) */,
+    GW_SPAN_STEP_LOOKAHEAD = 16 /* the two launches of one gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel) */
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -516,6 +518,49 @@ gw_status gw_fear_shield_joint(void *env, const int32_t *rl_actions, const int32
 gw_status gw_step_preview(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
                           uint16_t *outcome, double *reward_alt, uint16_t *crash9, uint16_t *safe_mask,
                           int32_t *actions, void *stream);
+
+/* The two-step crash lookahead: gw_step_preview's own-crash sets for the step that gw_step(env, rl_actions,
+ * scripted, ...) WOULD run next, and for the step after it, without moving the world.  The crash-aware shields
+ * look one step ahead, and a crash they flag unavoidable was usually avoidable one step earlier: the agent had
+ * stepped into a cell from which every action crashes.  Arguments and preconditions are gw_step_preview's.
+ * Stage 1, for every env e, RL agent k < K and first action a in 0..8, is exactly gw_step_preview's task: the real
+ *   world update of the step about to run under the joint action that step would apply (the proposals or the
+ *   step's own device-random draws, `scripted` or the step's Philox draws) with agent k playing a, eaters 0..K-1,
+ *   the env's apples still present.
+ * ends [E][K] u16: bit a set when that step ends the episode, by the step's own `done` rule: all terminated, or
+ *   all truncated, or t + 1 >= max_steps.  In the multi-agent variant any RL crash truncates every agent, so bit a
+ *   is also set where ANOTHER RL agent's crash ends the episode while k itself is fine; the all-eaten truncation
+ *   counts; variant 1 ends on the own crash or on the apple.
+ * Stage 2 runs only where bit a of ends is clear: the world is stage 1's final cells at time t + 1 of the same
+ *   episode.  Scripted agents n >= K play their Philox draw of step t + 1 from their stage-1 final cell (always the
+ *   Philox law: a caller's `scripted` override applies to stage 1 only); RL agent k plays b in 0..8; EVERY OTHER RL
+ *   AGENT PLAYS ACTION 0 (stay).  That is the one assumption: stage 2 is exact for K = 1, and wherever the others do
+ *   stay.  One real world update per (k, a, b).
+ * crash2 [E][K][9] u16: bit b of crash2[e][k][a] set when k itself crashes in stage 2; 0 where the step ends under a.
+ * crash9 [E][K] u16: gw_step_preview's, bit for bit.
+ * trap9 [E][K] u16: with mask2 the cell table's action-mask bits of k's stage-1 final cell under a (the mask the
+ *   step would return), bit a is set when the step does not end under a, mask2 != 0 and
+ *   (mask2 & ~crash2[e][k][a]) == 0: after a, every action that cell allows crashes k.
+ * ahead_mask [E][K] u16: m & ~crash9 & ~trap9 with m = mask[e][k] (mask [E][K] 9-bit action masks; NULL: 0x1FF);
+ *   where that is empty, gw_step_preview's safe_mask(m, crash9).  The rules are csrc/step_lookahead.h's.  Passed to
+ *   gw_fear_shield in the action mask's place it makes the shield avoid trap actions as well as crashes.
+ * Each of crash2, ends, crash9, trap9 and ahead_mask may be NULL; actions / mdr [E][N] i32 or NULL: the joint
+ * action that step will apply and the cells' MdR (gw_step_out.actions / .mdr).
+ * The promise: suppose the step applies the previewed joint action with k playing a, and the episode does not
+ * end.  Then crash2[e][k][a] is, bit for bit, the crash9[e][k] that gw_step_preview returns before the following
+ * step when every RL agent proposes 0.
+ * Conventions of gw_step_preview: works on cfg.fear == 0 envs; changes no env state, step output, pipeline state or
+ * obs-destination table; uses gw_step_preview's record buffer, allocated by the first call of either (a first call
+ * while `stream` captures returns GW_ERR_STATE, later calls can be captured); no host synchronisation;
+ * GW_ERR_STATE before the first gw_reset; GW_ERR_ARG on a null env or a u16 array that is not 2-byte aligned.
+ * Cost: two launches on `stream` (preview_rec_kernel, then step_lookahead_kernel: one wave per env; the K x 9
+ * stage-1 tasks dealt to its lanes, their final cells and the (N - K) x 9 K scripted draws of step t + 1 kept in
+ * LDS, then up to K x 81 stage-2 tasks, one register-resident world update per lane and turn), one
+ * GW_SPAN_STEP_LOOKAHEAD span while profiling; gw_count_sims counts 9 K + 9 x (the number of (k, a) whose step
+ * does not end) world updates per env. */
+gw_status gw_step_lookahead(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                            uint16_t *crash2, uint16_t *ends, uint16_t *crash9, uint16_t *trap9, uint16_t *ahead_mask,
+                            int32_t *actions, int32_t *mdr, void *stream);
 
 /* The coordinated crash-aware shield: gw_step_preview's safe masks inside gw_fear_shield_joint's sweeps, in one call.
  * The crash-aware shield built from gw_step_preview and gw_fear_shield is unilateral: an agent moved to a safe action

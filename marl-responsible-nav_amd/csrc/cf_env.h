@@ -539,6 +539,22 @@ struct StepPreviewArgs {
 hipError_t launch_step_preview(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
                                const StepPreviewArgs &a);
 
+// gw_step_lookahead's outputs beside the env's (include/gridenv.h): mask [E][K] or null, crash2 [E][K][9] /
+// ends [E][K] / crash9 [E][K] / trap9 [E][K] / ahead_mask [E][K] or null
+struct StepLookaheadArgs {
+    const uint16_t *mask;
+    uint16_t *crash2;
+    uint16_t *ends;
+    uint16_t *crash9;
+    uint16_t *trap9;
+    uint16_t *ahead_mask;
+};
+
+// step_lookahead_kernel<N> (step_lookahead.hip, gw_step_lookahead) over p's env range on s, through gwprof::launch,
+// from the record in p.fwork
+hipError_t launch_step_lookahead(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
+                                 const StepLookaheadArgs &a);
+
 // The arguments of the two joint shields beside the env's (include/gridenv.h; the kernels' one body:
 // shield_joint_core.h): mask [E][K] or null, probs [K][E][9] or null, agents / sweeps already checked,
 // actions_out [E][K], flags [E][K] / table [E][K][9] / joint [E][N] or null.  gw_crash_shield_joint alone reads

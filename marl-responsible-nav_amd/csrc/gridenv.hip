@@ -2987,6 +2987,25 @@ gw_status gw_step_preview(void *handle, const int32_t *rl_actions, const int32_t
                         });
 }
 
+gw_status gw_step_lookahead(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                            uint16_t *crash2, uint16_t *ends, uint16_t *crash9, uint16_t *trap9, uint16_t *ahead_mask,
+                            int32_t *actions, int32_t *mdr, void *stream) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_step_lookahead: null env");
+    for (const void *q : {(const void *)mask, (const void *)crash2, (const void *)ends, (const void *)crash9,
+                          (const void *)trap9, (const void *)ahead_mask})
+        if (reinterpret_cast<uintptr_t>(q) & 1u) return fail(GW_ERR_ARG, "gw_step_lookahead: a u16 array not 2-byte aligned");
+    // the kernel keeps a cell and an action in one u16 (cell | action << 12)
+    if (env->HW > 4096) return fail(GW_ERR_ARG, "gw_step_lookahead: needs H*W <= 4096");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const gw::StepLookaheadArgs a{mask, crash2, ends, crash9, trap9, ahead_mask};
+    // both steps' world updates on the record (step_lookahead.hip); gw_step_preview's record buffer
+    return preview_call(env, "gw_step_lookahead", &env->step_preview_rec, GW_SPAN_STEP_LOOKAHEAD, rl_actions, scripted,
+                        actions, mdr, s, [&](dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+                            return gw::launch_step_lookahead(env->N, grid, block, dyn, s, q, a);
+                        });
+}
+
 gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,
                           int32_t *actions, int32_t *mdr, void *stream) {
     Env *env = static_cast<Env *>(handle);

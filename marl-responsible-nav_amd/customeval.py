@@ -60,9 +60,17 @@ def main(argv=None):
                          "world update and keep the shield (or, without --shield, the actor) to actions under which "
                          "the agent itself does not crash; also prints how many proposals would have crashed and "
                          "how many of them were replaced.  Unilateral: not with --shield-mode joint")
+    ap.add_argument("--shield-lookahead", action="store_true",
+                    help="lookahead shield: the crash-aware shield looking two steps ahead; it also keeps an agent "
+                         "off trap actions, after which every action its new cell allows crashes it one step later "
+                         "(the other RL agents staying); implies --shield-crash and also prints how many proposals "
+                         "were trap actions and how many of them were replaced.  Unilateral: not with --shield-mode "
+                         "joint or joint_crash")
     args = ap.parse_args(argv)
     if args.shield_crash and args.shield_mode == "joint":
         ap.error("--shield-crash is unilateral: not with --shield-mode joint")
+    if args.shield_lookahead and args.shield_mode != "unilateral":
+        ap.error("--shield-lookahead is unilateral: not with --shield-mode joint or joint_crash")
 
     from marlnav import scenario as S
     from marlnav.evaluate import evaluate
@@ -85,7 +93,8 @@ def main(argv=None):
                  fear=args.feal or args.resp_full or resp_map or args.resp_footprint is not None,
                  seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield,
                  shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps, resp_map=resp_map,
-                 resp_footprint=args.resp_footprint, shield_crash=args.shield_crash)
+                 resp_footprint=args.resp_footprint, shield_crash=args.shield_crash,
+                 shield_lookahead=args.shield_lookahead)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
@@ -104,9 +113,12 @@ def main(argv=None):
               f"proposals would have crashed the agent, {r['shield_crash_final'].tolist()} applied actions did, "
               f"{r['shield_unavoidable'].tolist()} visits had no crash-free action, agent-steps per RL agent; "
               f"{r['shield_unconverged']} env-steps unconverged")
-    elif args.shield_crash:
+    elif args.shield_crash or args.shield_lookahead:
         print(f"Crash shield: {r['shield_crash_proposed'].tolist()} proposals would have crashed the agent, "
               f"{r['shield_crash_replaced'].tolist()} of them replaced, agent-steps per RL agent")
+    if args.shield_lookahead:
+        print(f"Lookahead shield: {r['shield_trap_proposed'].tolist()} proposals were trap actions, "
+              f"{r['shield_trap_replaced'].tolist()} of them replaced, agent-steps per RL agent")
     if args.feal:
         print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
     if args.resp_full:

@@ -37,7 +37,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
              variant: int = 0, resp_matrix: bool = False, fear_regret: bool = False,
              feal: bool = False, resp_full: bool = False, shield: float | None = None,
              shield_mode: str = "unilateral", shield_sweeps: int = 2, resp_map: bool = False,
-             resp_footprint: int | None = None, shield_crash: bool = False) -> dict:
+             resp_footprint: int | None = None, shield_crash: bool = False,
+             shield_lookahead: bool = False) -> dict:
     """The responsibility folds (marlnav/resp_folds.py: each class says what it sums), over the episodes still
     running; all but ``resp_matrix`` raise ValueError without ``fear=True``.  f64 / int64 CPU tensors:
       resp_matrix: "resp" [K, N], the summed rows divided by "steps".
@@ -61,8 +62,11 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
       shield_mode="joint_crash": the coordinated crash-aware shield (``VecGridEnv.crash_shield_joint``: the crash
         preview inside the joint sweeps); ``shield=None`` is crash-only, a tau adds FeAR; ``shield_crash`` is
         implied.  The joint mode's counts, "shield_crash_proposed" [K] (the proposal would have crashed the agent),
-        "shield_crash_final" [K] (the applied joint action does) and "shield_unavoidable" [K]."""
-    check_shield_args(shield_mode, shield_crash, "evaluate")
+        "shield_crash_final" [K] (the applied joint action does) and "shield_unavoidable" [K].
+      shield_lookahead: the lookahead shield (``VecGridEnv.step_lookahead``): the crash-aware shield that also keeps
+        off trap actions; ``shield_crash`` is implied; also "shield_trap_proposed" [K] and "shield_trap_replaced"
+        [K].  Unilateral: ValueError with ``shield_mode="joint"`` or ``"joint_crash"``."""
+    check_shield_args(shield_mode, shield_crash, "evaluate", shield_lookahead)
     for kw, on in (("fear_regret=True", fear_regret), ("feal=True", feal), ("resp_full=True", resp_full),
                    ("resp_map=True", resp_map), ("resp_footprint=R", resp_footprint is not None)):
         if on and not fear:
@@ -84,8 +88,9 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         lib = _lib.load()
         folds, cells = build_folds(env, "evaluate", resp_matrix, fear_regret, feal, resp_full, resp_map, resp_footprint)
         guard = None
-        if shield is not None or shield_crash or shield_mode == "joint_crash":
-            guard = Shield(env, shield, shield_mode, shield_sweeps, shield_crash, count_crash=True, who="evaluate")
+        if shield is not None or shield_crash or shield_lookahead or shield_mode == "joint_crash":
+            guard = Shield(env, shield, shield_mode, shield_sweeps, shield_crash, count_crash=True, who="evaluate",
+                           lookahead=shield_lookahead)
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):

@@ -215,10 +215,13 @@ def fold_results(folds, widths, flat, all_reduce=None) -> dict:
     return out
 
 
-def check_shield_args(shield_mode: str, shield_crash: bool, who: str = "Rollout"):
+def check_shield_args(shield_mode: str, shield_crash: bool, who: str = "Rollout", shield_lookahead: bool = False):
     """The shield keywords' checks (no device needed)."""
     if shield_mode not in ("unilateral", "joint", "joint_crash"):
         raise ValueError(f'{who}(shield_mode=...): "unilateral", "joint" or "joint_crash"')
+    if shield_lookahead and shield_mode != "unilateral":
+        raise ValueError(f'{who}(shield_lookahead=True) with shield_mode="{shield_mode}": the lookahead shield is '
+                         "unilateral")
     if shield_crash and shield_mode == "joint":
         raise ValueError(f'{who}(shield_crash=True) with shield_mode="joint": the crash-aware shield is unilateral')
 
@@ -243,6 +246,10 @@ class Shield:
         actions against the actions fixed so far.  ``tau=None`` is crash-only, a float adds FeAR (``table`` is then
         set); ``crash9`` holds the own-crash sets under the applied joint action, ``flags`` carries bits 4 (the
         agent crashes in the step) and 5 (its last visit had no crash-free masked action) too.
+      lookahead (``lookahead=True``, unilateral only; ``crash`` is implied): the crash-aware pipeline with
+        ``env.step_lookahead`` in ``step_preview``'s place and its "ahead_mask" in the safe mask's: the trap actions
+        (after which every action the agent's new cell allows crashes it in the step after, the other RL agents
+        staying) are taken out too.  ``trap9`` holds the last step's [E, K] trap sets.
     ``flags`` holds the last step's [E, K] uint8 flags.  ``totals()``: "shield_replaced" [K] and "shield_stuck"
     [K] (int64 CPU tensors: the agent-steps whose action was replaced, flag bit 0 / that had no allowed action,
     bit 1); joint: also "shield_over" [K] (the applied action's FeAR exceeds tau, bit 2) and
@@ -250,11 +257,15 @@ class Shield:
     "shield_crash_proposed" [K] and "shield_crash_replaced" [K] (the agent-steps whose proposed action would
     have crashed the agent itself / of those, the ones replaced); joint_crash: the joint mode's four counts,
     "shield_crash_proposed" [K] (agent k crashes in the step the proposal would have run), "shield_crash_final" [K]
-    (it crashes in the step that was run, bit 4) and "shield_unavoidable" [K] (bit 5)."""
+    (it crashes in the step that was run, bit 4) and "shield_unavoidable" [K] (bit 5); lookahead: also
+    "shield_trap_proposed" [K] and "shield_trap_replaced" [K] (the agent-steps whose proposed action was a trap
+    action / of those, the ones replaced)."""
 
     def __init__(self, env, tau: float | None, mode: str = "unilateral", sweeps: int = 2, crash: bool = False,
-                 count_crash: bool = False, who: str = "Rollout"):
-        check_shield_args(mode, crash, who)
+                 count_crash: bool = False, who: str = "Rollout", lookahead: bool = False):
+        check_shield_args(mode, crash, who, lookahead)
+        self.lookahead = bool(lookahead)
+        crash = bool(crash) or self.lookahead
         E, K, dev = env.E, env.K, env.device
         self.tau = None if tau is None else float(tau)
         self.joint_crash = mode == "joint_crash"
@@ -264,6 +275,9 @@ class Shield:
         self.cnt = torch.zeros((4 if self.joint else 2, K), dtype=torch.int64, device=dev)
         # crashing proposals, of those replaced
         self.crash_cnt = torch.zeros((2, K), dtype=torch.int64, device=dev) if crash and count_crash else None
+        # trap proposals, of those replaced
+        self.trap_cnt = torch.zeros((2, K), dtype=torch.int64, device=dev) if self.lookahead else None
+        self.trap9 = None
         if self.joint_crash:  # proposal crashes, final crashes, unavoidable
             self.crash_cnt = torch.zeros((3, K), dtype=torch.int64, device=dev)
             self._outcome_prop = torch.empty(E, dtype=torch.int16, device=dev)
@@ -311,16 +325,24 @@ class Shield:
             else:
                 env.fear_preview(actions, out=self._table)
         if self.crash:  # the shield picks among the actions under which the agent itself does not crash
-            sp = env.step_preview(actions, None, mask=mask, reward=False)
+            if self.lookahead:  # ... and that is no trap action
+                sp = env.step_lookahead(actions, None, mask=mask)
+            else:
+                sp = env.step_preview(actions, None, mask=mask, reward=False)
             if actions is None:
                 actions = sp["actions"][:, :env.K].contiguous()
-            mask, self.crash9 = sp["safe_mask"], sp["crash9"]
+            mask, self.crash9 = sp["ahead_mask" if self.lookahead else "safe_mask"], sp["crash9"]
+            self.trap9 = sp.get("trap9")
         out, flags = env.fear_shield(self._table, actions, mask=mask, probs=probs,
                                      tau=0.0 if self.tau is None else self.tau, out=self._out, flags=self.flags)
         if self.crash_cnt is not None:
             bad = (self.crash9.to(torch.int64) >> actions.to(torch.int64)) & 1
             count(self.crash_cnt[0], bad)
             count(self.crash_cnt[1], bad * (out != actions).to(torch.int64))
+        if self.trap_cnt is not None:
+            trap = (self.trap9.to(torch.int64) >> actions.to(torch.int64)) & 1
+            count(self.trap_cnt[0], trap)
+            count(self.trap_cnt[1], trap * (out != actions).to(torch.int64))
         count(self.cnt[0], flags & 1)
         count(self.cnt[1], flags >> 1)
         return out
@@ -334,6 +356,9 @@ class Shield:
         elif self.crash_cnt is not None:
             cc = _summed(self.crash_cnt, all_reduce)
             out["shield_crash_proposed"], out["shield_crash_replaced"] = cc[0], cc[1]
+        if self.trap_cnt is not None:
+            tc = _summed(self.trap_cnt, all_reduce)
+            out["shield_trap_proposed"], out["shield_trap_replaced"] = tc[0], tc[1]
         cnt = _summed(self.cnt, all_reduce)
         out["shield_replaced"], out["shield_stuck"] = cnt[0], cnt[1]
         if self.joint:

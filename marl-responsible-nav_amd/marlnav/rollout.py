@@ -214,7 +214,8 @@ class Rollout:
                  patch_async: bool | None = None, desc_ring: bool | str = False, resp_matrix: bool = False,
                  fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
                  shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2,
-                 resp_map: bool = False, resp_footprint: int | None = None, shield_crash: bool = False):
+                 resp_map: bool = False, resp_footprint: int | None = None, shield_crash: bool = False,
+                 shield_lookahead: bool = False):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -268,6 +269,10 @@ class Rollout:
             then set); ``shield_crash`` is implied.  ``shield_flags`` carries bits 4 (crashes in the step) and 5
             (unavoidable) too, ``shield_crash9`` the own-crash sets under the applied joint action; totals: the
             joint mode's, "shield_crash_proposed" [K], "shield_crash_final" [K], "shield_unavoidable" [K].
+          shield_lookahead: the lookahead shield (``env.step_lookahead``): the crash-aware shield that also keeps
+            off trap actions, after which every allowed action crashes the agent one step later; ``shield_crash``
+            is implied; ``shield_trap9`` holds the last step's [E, K] trap sets; also "shield_trap_proposed" [K],
+            "shield_trap_replaced" [K].  Unilateral: ValueError with ``shield_mode="joint"`` or ``"joint_crash"``.
         Eager only: ``capture`` raises ValueError."""
         self.env = env
         self.actors = actors
@@ -346,18 +351,21 @@ class Rollout:
         self._pending = None  # (stats, tick) of a step whose FeAR may still be in flight
         self._folds, self._cells = build_folds(env, "Rollout", resp_matrix, fear_regret, feal, resp_full, resp_map,
                                                resp_footprint)
-        self.check_shield_args(shield_mode, shield_crash)
+        self.check_shield_args(shield_mode, shield_crash, "Rollout", shield_lookahead)
         self.shield = None if shield is None else float(shield)
-        self.shield_mode, self.shield_sweeps, self.shield_crash = shield_mode, int(shield_sweeps), bool(shield_crash)
+        self.shield_lookahead = bool(shield_lookahead)
+        self.shield_mode, self.shield_sweeps = shield_mode, int(shield_sweeps)
+        self.shield_crash = bool(shield_crash) or self.shield_lookahead
         self._shield = None
         if self.shield is not None or self.shield_crash or shield_mode == "joint_crash":
-            self._shield = Shield(env, self.shield, shield_mode, shield_sweeps, self.shield_crash)
+            self._shield = Shield(env, self.shield, shield_mode, shield_sweeps, self.shield_crash,
+                                  lookahead=self.shield_lookahead)
 
     check_shield_args = staticmethod(check_shield_args)
 
     # the shield's last-step tensors (None without a shield / outside the mode that fills them)
-    shield_flags, shield_table, shield_crash9 = (property(lambda self, n=n: getattr(self._shield, n, None))
-                                                 for n in ("flags", "table", "crash9"))
+    shield_flags, shield_table, shield_crash9, shield_trap9 = (
+        property(lambda self, n=n: getattr(self._shield, n, None)) for n in ("flags", "table", "crash9", "trap9"))
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0

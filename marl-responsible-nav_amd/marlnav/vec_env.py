@@ -829,6 +829,45 @@ class VecGridEnv:
                        "gw_step_preview")
         return {n: t for n, t in buf.items() if t is not None and (reward or n != "reward_alt")}
 
+    def step_lookahead(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
+                       mask: torch.Tensor | None = None) -> dict:
+        """The two-step crash lookahead (gw_step_lookahead): ``step_preview``'s own-crash sets for the step that
+        ``step(rl_actions, scripted)`` would run and for the step after it, without moving the world.  -> a dict of
+        tensors, allocated once and reused by every call:
+          "crash2" [E, K, 9] int16: bit b of entry (k, a) = agent k itself crashes in the step after, playing b
+            from the cell that first action a leaves it in, while the other RL agents stay (action 0) and the
+            scripted agents play their draws of that step; 0 where the step ends the episode under a;
+          "ends" [E, K] int16: bit a = the step ends the episode with agent k playing a (another RL agent's crash
+            and the step cap included);
+          "crash9" [E, K] int16: ``step_preview``'s, bit a = agent k itself crashes in the step under a;
+          "trap9" [E, K] int16: bit a = the step goes on under a and every action the cell after it allows
+            crashes k;
+          "ahead_mask" [E, K] int16: ``mask & ~crash9 & ~trap9`` (mask None: all nine); where that is empty,
+            ``step_preview``'s safe mask;
+          "actions" [E, N] int32: the joint action that step will apply.
+        None arguments mean what they mean for ``step``; a ``scripted`` override holds for the first step only.
+        Works with ``fear=False``.  Changes no env state."""
+        E, K, N = self.E, self.K, self.N
+        self._check_counts("step_lookahead", rl_actions=(rl_actions, E * K), scripted=(scripted, E * (N - K)))
+        self._check_bufs("step_lookahead", dict(mask=mask), dict(mask=(torch.int16, E * K)), self.device,
+                         note=" (the 9-bit action masks, as StepResult.mask)")
+        rl = self._as_i32(rl_actions, (E, K))
+        sa = self._as_i32(scripted, (E, N - K))
+        buf = getattr(self, "_step_lookahead_out", None)
+        if buf is None:
+            i16 = dict(dtype=torch.int16, device=self.device)
+            buf = dict(crash2=torch.zeros((E, K, 9), **i16), ends=torch.zeros((E, K), **i16),
+                       crash9=torch.zeros((E, K), **i16), trap9=torch.zeros((E, K), **i16),
+                       ahead_mask=torch.zeros((E, K), **i16),
+                       actions=torch.zeros((E, N), dtype=torch.int32, device=self.device))
+            self._step_lookahead_out = buf
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_step_lookahead(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), _ptr(buf["crash2"]),
+                                                  _ptr(buf["ends"]), _ptr(buf["crash9"]), _ptr(buf["trap9"]),
+                                                  _ptr(buf["ahead_mask"]), _ptr(buf["actions"]), None,
+                                                  self._stream()), "gw_step_lookahead")
+        return dict(buf)
+
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
         """Egocentric local observations (gw_obs_patch): [K, E, size, size] float32, agent k's obs
