@@ -167,7 +167,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * GW_SPAN_FEAR_SHIELD the two launches of gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel),
  * GW_SPAN_STEP_PREVIEW the two launches of gw_step_preview (preview_rec_kernel, step_preview_kernel),
  * GW_SPAN_CRASH_SHIELD the two launches of gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel),
- * GW_SPAN_STEP_LOOKAHEAD the two launches of gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel).
+ * GW_SPAN_STEP_LOOKAHEAD the two launches of gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel),
+ * GW_SPAN_STEP_HORIZON the two launches of gw_step_horizon (preview_rec_kernel, step_horizon_kernel).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -179,7 +180,8 @@ enum {
     GW_SPAN_FEAR_SHIELD = 13 /* the two launches of one gw_fear_shield_joint (preview_rec_kernel, fear_shield_joint_kernel) */,
     GW_SPAN_STEP_PREVIEW = 14 /* the two launches of one gw_step_preview (preview_rec_kernel, step_preview_kernel) */,
     GW_SPAN_CRASH_SHIELD = 15 /* the two launches of one gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel) */,
-    GW_SPAN_STEP_LOOKAHEAD = 16 /* the two launches of one gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel) */
+    GW_SPAN_STEP_LOOKAHEAD = 16 /* the two launches of one gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel) */,
+    GW_SPAN_STEP_HORIZON = 17 /* the two launches of one gw_step_horizon (preview_rec_kernel, step_horizon_kernel) */
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -561,6 +563,53 @@ gw_status gw_step_preview(void *env, const int32_t *rl_actions, const int32_t *s
 gw_status gw_step_lookahead(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
                             uint16_t *crash2, uint16_t *ends, uint16_t *crash9, uint16_t *trap9, uint16_t *ahead_mask,
                             int32_t *actions, int32_t *mdr, void *stream);
+
+/* The crash horizon: for each RL agent k and first action a, how many of the next H steps k can survive, without
+ * moving the world.  gw_step_lookahead looks two steps ahead; most agent-steps it leaves without a crash-free,
+ * trap-free action need a longer horizon.  `horizon` is H, 2 <= H <= GW_HORIZON_MAX.  Arguments and preconditions
+ * are gw_step_lookahead's.
+ * Step 1, for every env e, RL agent k < K and first action a in 0..8, is exactly gw_step_preview's task: the real
+ *   world update of the step about to run under the joint action that step would apply (`scripted` or the step's
+ *   Philox draws) with agent k playing a, eaters 0..K-1, the env's apples still present.  crash9 [E][K] u16 and
+ *   ends [E][K] u16 are gw_step_lookahead's, bit for bit.
+ * Steps 2..H exist only while the episode goes on.  In step i the scripted agents n >= K play their Philox draw of
+ *   step t + i - 1 from their own cells (always the Philox law: a caller's `scripted` override applies to step 1
+ *   only), agent k plays an action b that the cell table's action-mask bits of the cell it stands in allow (the
+ *   mask2 rule of trap9), and EVERY OTHER RL AGENT PLAYS ACTION 0 (stay).  That is the one assumption: the steps are
+ *   exact for K = 1, and wherever the others do stay.  There are no apples after step 1: a later step ends the
+ *   episode only by an RL agent's crash or by the step cap (t + i >= max_steps, max_steps > 0).  This is
+ *   conservative: an all-eaten end after step 1, which would count as survival, is ignored.
+ * depth [E][K][9] u8 in 0..H: the largest d for which some continuation exists in which k itself does not crash in
+ *   the steps 1..d.  A continuation that reaches an episode end without k's own crash (another RL agent's crash,
+ *   the cap, an apple or all-eaten end of step 1) counts as H; so does one that leaves k in a cell whose action
+ *   mask is empty (trap9 reads an empty mask2 the same way).  At H = 2: depth 0 = a crashes k (crash9), depth 1 =
+ *   a is a trap action (gw_step_lookahead's trap9), depth 2 = neither.
+ * viable9 [E][K] u16: bit a set iff depth[e][k][a] == H.
+ * horizon_mask [E][K] u16: with m = mask[e][k] (mask [E][K] 9-bit action masks; NULL: 0x1FF), the actions of m whose
+ *   depth is the maximum over m; m == 0 gives 0.  At H = 2 it equals gw_step_lookahead's ahead_mask bit for bit.
+ *   The rules are csrc/step_horizon.h's.  Passed to gw_fear_shield in the action mask's place it makes the shield
+ *   pick among the actions that keep the agent alive longest.
+ * Each of depth, ends, crash9, viable9 and horizon_mask may be NULL; actions / mdr [E][N] i32 or NULL: the joint
+ * action that step will apply and the cells' MdR (gw_step_out.actions / .mdr).
+ * How it is computed: while k has not crashed the world differs between k's choices in k's own cell only (an agent
+ * changes another agent's cell only through a collision, a collision marks both agents crashed, and an RL crash
+ * ends the episode), so level h (the world after h survived steps) is one background, the other agents' cells and
+ * actions, and a set of distinct cells of k within Manhattan distance 2 h.
+ * Conventions of gw_step_lookahead: works on cfg.fear == 0 envs; changes no env state, step output, pipeline state
+ * or obs-destination table; uses gw_step_preview's record buffer, allocated by the first call of any of the three
+ * (a first call while `stream` captures returns GW_ERR_STATE, later calls can be captured); no host
+ * synchronisation; GW_ERR_STATE before the first gw_reset; GW_ERR_ARG on a null env (before any device use), a
+ * horizon outside 2..GW_HORIZON_MAX or a u16 array that is not 2-byte aligned.
+ * Cost: two launches on `stream` (preview_rec_kernel, then step_horizon_kernel: one wave per env, the RL agents in
+ * turn), one GW_SPAN_STEP_HORIZON span while profiling.  gw_count_sims counts, per env, 9 K for step 1 plus, for
+ * each k and each level h = 1..H - 1 that is reached (some first action, or some update of level h - 1, left k
+ * uncrashed with the episode going on), one world update per distinct cell k can stand in at that level and per
+ * action that cell's mask allows.  Every update is counted once; a level's background needs no update of its own
+ * (it is read from the lowest-numbered update of the level before that goes on). */
+#define GW_HORIZON_MAX 4
+gw_status gw_step_horizon(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask, int horizon,
+                          uint8_t *depth, uint16_t *ends, uint16_t *crash9, uint16_t *viable9, uint16_t *horizon_mask,
+                          int32_t *actions, int32_t *mdr, void *stream);
 
 /* The coordinated crash-aware shield: gw_step_preview's safe masks inside gw_fear_shield_joint's sweeps, in one call.
  * The crash-aware shield built from gw_step_preview and gw_fear_shield is unilateral: an agent moved to a safe action

@@ -555,6 +555,23 @@ struct StepLookaheadArgs {
 hipError_t launch_step_lookahead(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
                                  const StepLookaheadArgs &a);
 
+// gw_step_horizon's arguments beside the env's (include/gridenv.h): mask [E][K] or null, horizon in
+// 2..GW_HORIZON_MAX, depth [E][K][9] / ends [E][K] / crash9 [E][K] / viable9 [E][K] / horizon_mask [E][K] or null
+struct StepHorizonArgs {
+    const uint16_t *mask;
+    int horizon;
+    uint8_t *depth;
+    uint16_t *ends;
+    uint16_t *crash9;
+    uint16_t *viable9;
+    uint16_t *horizon_mask;
+};
+
+// step_horizon_kernel<N> (step_horizon.hip, gw_step_horizon) over p's env range on s, through gwprof::launch,
+// from the record in p.fwork
+hipError_t launch_step_horizon(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
+                               const StepHorizonArgs &a);
+
 // The arguments of the two joint shields beside the env's (include/gridenv.h; the kernels' one body:
 // shield_joint_core.h): mask [E][K] or null, probs [K][E][9] or null, agents / sweeps already checked,
 // actions_out [E][K], flags [E][K] / table [E][K][9] / joint [E][N] or null.  gw_crash_shield_joint alone reads

@@ -3006,6 +3006,26 @@ gw_status gw_step_lookahead(void *handle, const int32_t *rl_actions, const int32
                         });
 }
 
+gw_status gw_step_horizon(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask,
+                          int horizon, uint8_t *depth, uint16_t *ends, uint16_t *crash9, uint16_t *viable9,
+                          uint16_t *horizon_mask, int32_t *actions, int32_t *mdr, void *stream) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_step_horizon: null env");
+    if (horizon < 2 || horizon > GW_HORIZON_MAX) return fail(GW_ERR_ARG, "gw_step_horizon: need 2 <= horizon <= GW_HORIZON_MAX");
+    for (const void *q : {(const void *)mask, (const void *)ends, (const void *)crash9, (const void *)viable9,
+                          (const void *)horizon_mask})
+        if (reinterpret_cast<uintptr_t>(q) & 1u) return fail(GW_ERR_ARG, "gw_step_horizon: a u16 array not 2-byte aligned");
+    // the kernel keeps a cell and an action in one u16 (cell | action << 12)
+    if (env->HW > 4096) return fail(GW_ERR_ARG, "gw_step_horizon: needs H*W <= 4096");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const gw::StepHorizonArgs a{mask, horizon, depth, ends, crash9, viable9, horizon_mask};
+    // every level's world updates on the record (step_horizon.hip); gw_step_preview's record buffer
+    return preview_call(env, "gw_step_horizon", &env->step_preview_rec, GW_SPAN_STEP_HORIZON, rl_actions, scripted,
+                        actions, mdr, s, [&](dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+                            return gw::launch_step_horizon(env->N, grid, block, dyn, s, q, a);
+                        });
+}
+
 gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,
                           int32_t *actions, int32_t *mdr, void *stream) {
     Env *env = static_cast<Env *>(handle);

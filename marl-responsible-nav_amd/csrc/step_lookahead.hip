@@ -17,32 +17,7 @@
 namespace gw {
 
 #include "draw_action.h"
-
-// Orders one wave's LDS accesses (shield_joint_core.h's rule restated: the LDS serves a wave's instructions in
-// issue order, so it is enough to keep the compiler from moving an access across this point).
-__device__ __forceinline__ void lookahead_lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// The step's `done` (finish_env, gridenv.hip; agent.py:241-243) restated for one world update, nothing stored:
-// all terminated, or all truncated, or the step cap.  flags: the env's apples | term << 8 | trunc << 16 before
-// the step; caught / crash: simulate's; t: the env's step count before the step.
-__device__ __forceinline__ bool preview_done(const Params &p, int K, uint32_t flags, uint32_t caught, uint32_t crash,
-                                             int t) {
-    const bool single = p.variant == 1;
-    uint32_t apples = flags & 0xFFu, term = (flags >> 8) & 0xFFu, trunc = (flags >> 16) & 0xFFu;
-    const uint32_t allk = (1u << K) - 1u;
-    const uint32_t popped = single ? (((caught >> 8) == 1u) ? (caught & apples & 1u) : 0u) : (caught & apples & 0xFFu);
-    apples &= ~popped;
-    if (popped && apples == 0u) trunc = single ? (trunc | 1u) : allk;  // all eaten
-    const uint32_t own = crash & allk;                                  // the RL agents that crash
-    if (own) {
-        term |= own;
-        if (!single) trunc = allk;  // any RL crash truncates every agent (ma_customenv.py:281-285)
-    }
-    return ((term & allk) == allk) || ((trunc & allk) == allk) || (p.max_steps > 0 && t + 1 >= p.max_steps);
-}
+#include "preview_done.h"
 
 // gw_step_lookahead's action masks after the first step, as step_lookahead::rules reads them: entry a is the cell
 // table's action-mask bits of agent k's cell in the world (k, a)

@@ -66,7 +66,20 @@ def main(argv=None):
                          "(the other RL agents staying); implies --shield-crash and also prints how many proposals "
                          "were trap actions and how many of them were replaced.  Unilateral: not with --shield-mode "
                          "joint or joint_crash")
+    ap.add_argument("--shield-horizon", type=int, default=None, metavar="H",
+                    help="horizon shield (H in 2..4; default off): the crash-aware shield looking H steps ahead; it "
+                         "keeps an agent to the actions that keep it alive longest (the other RL agents staying "
+                         "after the first step); implies --shield-crash and also prints how many proposals were "
+                         "doomed, how many of them were replaced and how many agent-steps had no viable action.  "
+                         "Unilateral: not with --shield-mode joint or joint_crash, nor with --shield-lookahead")
     args = ap.parse_args(argv)
+    if args.shield_horizon is not None:
+        if not 2 <= args.shield_horizon <= 4:
+            ap.error("--shield-horizon: 2, 3 or 4")
+        if args.shield_mode != "unilateral":
+            ap.error("--shield-horizon is unilateral: not with --shield-mode joint or joint_crash")
+        if args.shield_lookahead:
+            ap.error("--shield-horizon 2 is --shield-lookahead: pick one")
     if args.shield_crash and args.shield_mode == "joint":
         ap.error("--shield-crash is unilateral: not with --shield-mode joint")
     if args.shield_lookahead and args.shield_mode != "unilateral":
@@ -94,7 +107,7 @@ def main(argv=None):
                  seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield,
                  shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps, resp_map=resp_map,
                  resp_footprint=args.resp_footprint, shield_crash=args.shield_crash,
-                 shield_lookahead=args.shield_lookahead)
+                 shield_lookahead=args.shield_lookahead, shield_horizon=args.shield_horizon)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
@@ -113,12 +126,16 @@ def main(argv=None):
               f"proposals would have crashed the agent, {r['shield_crash_final'].tolist()} applied actions did, "
               f"{r['shield_unavoidable'].tolist()} visits had no crash-free action, agent-steps per RL agent; "
               f"{r['shield_unconverged']} env-steps unconverged")
-    elif args.shield_crash or args.shield_lookahead:
+    elif args.shield_crash or args.shield_lookahead or args.shield_horizon is not None:
         print(f"Crash shield: {r['shield_crash_proposed'].tolist()} proposals would have crashed the agent, "
               f"{r['shield_crash_replaced'].tolist()} of them replaced, agent-steps per RL agent")
     if args.shield_lookahead:
         print(f"Lookahead shield: {r['shield_trap_proposed'].tolist()} proposals were trap actions, "
               f"{r['shield_trap_replaced'].tolist()} of them replaced, agent-steps per RL agent")
+    if args.shield_horizon is not None:
+        print(f"Horizon shield (H = {args.shield_horizon}): {r['shield_doomed_proposed'].tolist()} proposals were "
+              f"doomed, {r['shield_doomed_replaced'].tolist()} of them replaced, "
+              f"{r['shield_no_viable'].tolist()} had no viable action, agent-steps per RL agent")
     if args.feal:
         print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
     if args.resp_full:

@@ -38,7 +38,7 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
              feal: bool = False, resp_full: bool = False, shield: float | None = None,
              shield_mode: str = "unilateral", shield_sweeps: int = 2, resp_map: bool = False,
              resp_footprint: int | None = None, shield_crash: bool = False,
-             shield_lookahead: bool = False) -> dict:
+             shield_lookahead: bool = False, shield_horizon: int | None = None) -> dict:
     """The responsibility folds (marlnav/resp_folds.py: each class says what it sums), over the episodes still
     running; all but ``resp_matrix`` raise ValueError without ``fear=True``.  f64 / int64 CPU tensors:
       resp_matrix: "resp" [K, N], the summed rows divided by "steps".
@@ -65,8 +65,13 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         "shield_crash_final" [K] (the applied joint action does) and "shield_unavoidable" [K].
       shield_lookahead: the lookahead shield (``VecGridEnv.step_lookahead``): the crash-aware shield that also keeps
         off trap actions; ``shield_crash`` is implied; also "shield_trap_proposed" [K] and "shield_trap_replaced"
-        [K].  Unilateral: ValueError with ``shield_mode="joint"`` or ``"joint_crash"``."""
-    check_shield_args(shield_mode, shield_crash, "evaluate", shield_lookahead)
+        [K].  Unilateral: ValueError with ``shield_mode="joint"`` or ``"joint_crash"``.
+      shield_horizon: the horizon shield (``VecGridEnv.step_horizon``, an int H in 2..4): the crash-aware shield that
+        picks among the masked actions that keep the agent alive longest over H steps; ``shield_crash`` is implied;
+        also "shield_doomed_proposed" [K] (the proposal's depth was below H while a viable action existed),
+        "shield_doomed_replaced" [K] and "shield_no_viable" [K].  Unilateral: ValueError with a joint mode or
+        with ``shield_lookahead=True``."""
+    check_shield_args(shield_mode, shield_crash, "evaluate", shield_lookahead, shield_horizon)
     for kw, on in (("fear_regret=True", fear_regret), ("feal=True", feal), ("resp_full=True", resp_full),
                    ("resp_map=True", resp_map), ("resp_footprint=R", resp_footprint is not None)):
         if on and not fear:
@@ -88,9 +93,10 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         lib = _lib.load()
         folds, cells = build_folds(env, "evaluate", resp_matrix, fear_regret, feal, resp_full, resp_map, resp_footprint)
         guard = None
-        if shield is not None or shield_crash or shield_lookahead or shield_mode == "joint_crash":
+        if (shield is not None or shield_crash or shield_lookahead or shield_horizon is not None
+                or shield_mode == "joint_crash"):
             guard = Shield(env, shield, shield_mode, shield_sweeps, shield_crash, count_crash=True, who="evaluate",
-                           lookahead=shield_lookahead)
+                           lookahead=shield_lookahead, horizon=shield_horizon)
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):

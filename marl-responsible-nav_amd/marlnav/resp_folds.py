@@ -204,6 +204,9 @@ def fold_parts(folds):
     return [p for ps in parts for p in ps], [sum(p.numel() for p in ps) for ps in parts]
 
 
+GW_HORIZON_MAX = 4  # include/gridenv.h
+
+
 def fold_results(folds, widths, flat, all_reduce=None) -> dict:
     """Every fold's result keys: fold i reads the next ``widths[i]`` doubles of ``flat`` (``fold_parts``
     concatenated and summed over the ranks).  ``all_reduce`` (several ranks: an in-place sum, None otherwise) is
@@ -215,8 +218,18 @@ def fold_results(folds, widths, flat, all_reduce=None) -> dict:
     return out
 
 
-def check_shield_args(shield_mode: str, shield_crash: bool, who: str = "Rollout", shield_lookahead: bool = False):
+def check_shield_args(shield_mode: str, shield_crash: bool, who: str = "Rollout", shield_lookahead: bool = False,
+                      shield_horizon: int | None = None):
     """The shield keywords' checks (no device needed)."""
+    if shield_horizon is not None:
+        if isinstance(shield_horizon, bool) or not 2 <= int(shield_horizon) <= GW_HORIZON_MAX:
+            raise ValueError(f"{who}(shield_horizon=...): None or an int in 2..{GW_HORIZON_MAX}")
+        if shield_lookahead:
+            raise ValueError(f"{who}(shield_horizon={shield_horizon}) with shield_lookahead=True: the horizon shield at "
+                             "horizon 2 is the lookahead shield; pick one")
+        if shield_mode in ("joint", "joint_crash"):
+            raise ValueError(f'{who}(shield_horizon={shield_horizon}) with shield_mode="{shield_mode}": the horizon '
+                             "shield is unilateral")
     if shield_mode not in ("unilateral", "joint", "joint_crash"):
         raise ValueError(f'{who}(shield_mode=...): "unilateral", "joint" or "joint_crash"')
     if shield_lookahead and shield_mode != "unilateral":
@@ -250,6 +263,10 @@ class Shield:
         ``env.step_lookahead`` in ``step_preview``'s place and its "ahead_mask" in the safe mask's: the trap actions
         (after which every action the agent's new cell allows crashes it in the step after, the other RL agents
         staying) are taken out too.  ``trap9`` holds the last step's [E, K] trap sets.
+      horizon (``horizon=H``, unilateral only; ``crash`` is implied): the crash-aware pipeline with
+        ``env.step_horizon(horizon=H)`` in ``step_preview``'s place and its "horizon_mask" (the masked actions that
+        keep the agent alive longest over H steps, the other RL agents staying after the first) in the safe
+        mask's.  ``depth`` / ``viable9`` hold the last step's [E, K, 9] depths and [E, K] viable sets.
     ``flags`` holds the last step's [E, K] uint8 flags.  ``totals()``: "shield_replaced" [K] and "shield_stuck"
     [K] (int64 CPU tensors: the agent-steps whose action was replaced, flag bit 0 / that had no allowed action,
     bit 1); joint: also "shield_over" [K] (the applied action's FeAR exceeds tau, bit 2) and
@@ -259,13 +276,16 @@ class Shield:
     "shield_crash_proposed" [K] (agent k crashes in the step the proposal would have run), "shield_crash_final" [K]
     (it crashes in the step that was run, bit 4) and "shield_unavoidable" [K] (bit 5); lookahead: also
     "shield_trap_proposed" [K] and "shield_trap_replaced" [K] (the agent-steps whose proposed action was a trap
-    action / of those, the ones replaced)."""
+    action / of those, the ones replaced); horizon: also "shield_doomed_proposed" [K] (the proposal's depth was
+    below H while some action of the mask was viable), "shield_doomed_replaced" [K] (of those, the ones replaced)
+    and "shield_no_viable" [K] (no action of the mask was viable)."""
 
     def __init__(self, env, tau: float | None, mode: str = "unilateral", sweeps: int = 2, crash: bool = False,
-                 count_crash: bool = False, who: str = "Rollout", lookahead: bool = False):
-        check_shield_args(mode, crash, who, lookahead)
+                 count_crash: bool = False, who: str = "Rollout", lookahead: bool = False, horizon: int | None = None):
+        check_shield_args(mode, crash, who, lookahead, horizon)
         self.lookahead = bool(lookahead)
-        crash = bool(crash) or self.lookahead
+        self.horizon = None if horizon is None else int(horizon)
+        crash = bool(crash) or self.lookahead or self.horizon is not None
         E, K, dev = env.E, env.K, env.device
         self.tau = None if tau is None else float(tau)
         self.joint_crash = mode == "joint_crash"
@@ -278,6 +298,9 @@ class Shield:
         # trap proposals, of those replaced
         self.trap_cnt = torch.zeros((2, K), dtype=torch.int64, device=dev) if self.lookahead else None
         self.trap9 = None
+        # doomed proposals, of those replaced, agent-steps without a viable action
+        self.doomed_cnt = torch.zeros((3, K), dtype=torch.int64, device=dev) if self.horizon is not None else None
+        self.depth = self.viable9 = None
         if self.joint_crash:  # proposal crashes, final crashes, unavoidable
             self.crash_cnt = torch.zeros((3, K), dtype=torch.int64, device=dev)
             self._outcome_prop = torch.empty(E, dtype=torch.int16, device=dev)
@@ -325,13 +348,18 @@ class Shield:
             else:
                 env.fear_preview(actions, out=self._table)
         if self.crash:  # the shield picks among the actions under which the agent itself does not crash
-            if self.lookahead:  # ... and that is no trap action
+            m_in = mask
+            if self.horizon is not None:  # ... and that keeps the agent alive longest
+                sp = env.step_horizon(actions, None, mask=mask, horizon=self.horizon)
+                self.depth, self.viable9 = sp["depth"], sp["viable9"]
+            elif self.lookahead:  # ... and that is no trap action
                 sp = env.step_lookahead(actions, None, mask=mask)
             else:
                 sp = env.step_preview(actions, None, mask=mask, reward=False)
             if actions is None:
                 actions = sp["actions"][:, :env.K].contiguous()
-            mask, self.crash9 = sp["ahead_mask" if self.lookahead else "safe_mask"], sp["crash9"]
+            which = "horizon_mask" if self.horizon is not None else "ahead_mask" if self.lookahead else "safe_mask"
+            mask, self.crash9 = sp[which], sp["crash9"]
             self.trap9 = sp.get("trap9")
         out, flags = env.fear_shield(self._table, actions, mask=mask, probs=probs,
                                      tau=0.0 if self.tau is None else self.tau, out=self._out, flags=self.flags)
@@ -343,6 +371,13 @@ class Shield:
             trap = (self.trap9.to(torch.int64) >> actions.to(torch.int64)) & 1
             count(self.trap_cnt[0], trap)
             count(self.trap_cnt[1], trap * (out != actions).to(torch.int64))
+        if self.doomed_cnt is not None:
+            via = self.viable9.to(torch.int64) & (0x1FF if m_in is None else m_in.to(torch.int64) & 0x1FF)
+            some = (via != 0).to(torch.int64)
+            doomed = (1 - ((self.viable9.to(torch.int64) >> actions.to(torch.int64)) & 1)) * some
+            count(self.doomed_cnt[0], doomed)
+            count(self.doomed_cnt[1], doomed * (out != actions).to(torch.int64))
+            count(self.doomed_cnt[2], 1 - some)
         count(self.cnt[0], flags & 1)
         count(self.cnt[1], flags >> 1)
         return out
@@ -359,6 +394,9 @@ class Shield:
         if self.trap_cnt is not None:
             tc = _summed(self.trap_cnt, all_reduce)
             out["shield_trap_proposed"], out["shield_trap_replaced"] = tc[0], tc[1]
+        if self.doomed_cnt is not None:
+            dc = _summed(self.doomed_cnt, all_reduce)
+            out["shield_doomed_proposed"], out["shield_doomed_replaced"], out["shield_no_viable"] = dc[0], dc[1], dc[2]
         cnt = _summed(self.cnt, all_reduce)
         out["shield_replaced"], out["shield_stuck"] = cnt[0], cnt[1]
         if self.joint:

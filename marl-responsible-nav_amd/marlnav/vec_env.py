@@ -868,6 +868,46 @@ class VecGridEnv:
                                                   self._stream()), "gw_step_lookahead")
         return dict(buf)
 
+    def step_horizon(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
+                     mask: torch.Tensor | None = None, horizon: int = 3) -> dict:
+        """The crash horizon (gw_step_horizon): for each RL agent and first action, how many of the next ``horizon``
+        steps (2..4) the agent can survive, without moving the world.  -> a dict of tensors, allocated once and
+        reused by every call:
+          "depth" [E, K, 9] uint8 in 0..horizon: the largest d such that some continuation keeps agent k from
+            crashing in the steps 1..d after first action a; after the first step the other RL agents stay
+            (action 0), the scripted agents play their draws, and k plays what its cell's action mask allows.  An
+            episode end without k's own crash counts as ``horizon``;
+          "ends" / "crash9" [E, K] int16: ``step_lookahead``'s, bit for bit;
+          "viable9" [E, K] int16: bit a = depth == horizon;
+          "horizon_mask" [E, K] int16: the actions of ``mask`` (None: all nine) whose depth is the largest over
+            the mask; at horizon 2 it is ``step_lookahead``'s "ahead_mask";
+          "actions" [E, N] / "mdr" [E, N] int32: the joint action that step will apply and the cells' MdR.
+        None arguments mean what they mean for ``step``; a ``scripted`` override holds for the first step only.
+        Works with ``fear=False``.  Changes no env state."""
+        E, K, N = self.E, self.K, self.N
+        if isinstance(horizon, bool) or not 2 <= int(horizon) <= 4:
+            raise ValueError("step_horizon(horizon=...): an int in 2..4 (GW_HORIZON_MAX)")
+        self._check_counts("step_horizon", rl_actions=(rl_actions, E * K), scripted=(scripted, E * (N - K)))
+        self._check_bufs("step_horizon", dict(mask=mask), dict(mask=(torch.int16, E * K)), self.device,
+                         note=" (the 9-bit action masks, as StepResult.mask)")
+        rl = self._as_i32(rl_actions, (E, K))
+        sa = self._as_i32(scripted, (E, N - K))
+        buf = getattr(self, "_step_horizon_out", None)
+        if buf is None:
+            i16 = dict(dtype=torch.int16, device=self.device)
+            i32 = dict(dtype=torch.int32, device=self.device)
+            buf = dict(depth=torch.zeros((E, K, 9), dtype=torch.uint8, device=self.device),
+                       ends=torch.zeros((E, K), **i16), crash9=torch.zeros((E, K), **i16),
+                       viable9=torch.zeros((E, K), **i16), horizon_mask=torch.zeros((E, K), **i16),
+                       actions=torch.zeros((E, N), **i32), mdr=torch.zeros((E, N), **i32))
+            self._step_horizon_out = buf
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_step_horizon(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), int(horizon),
+                                                _ptr(buf["depth"]), _ptr(buf["ends"]), _ptr(buf["crash9"]),
+                                                _ptr(buf["viable9"]), _ptr(buf["horizon_mask"]), _ptr(buf["actions"]),
+                                                _ptr(buf["mdr"]), self._stream()), "gw_step_horizon")
+        return dict(buf)
+
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
         """Egocentric local observations (gw_obs_patch): [K, E, size, size] float32, agent k's obs
