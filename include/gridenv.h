@@ -168,7 +168,8 @@ gw_status gw_copy_state(void *env, const gw_state *buf, int to_env, void *stream
  * GW_SPAN_STEP_PREVIEW the two launches of gw_step_preview (preview_rec_kernel, step_preview_kernel),
  * GW_SPAN_CRASH_SHIELD the two launches of gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel),
  * GW_SPAN_STEP_LOOKAHEAD the two launches of gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel),
- * GW_SPAN_STEP_HORIZON the two launches of gw_step_horizon (preview_rec_kernel, step_horizon_kernel).
+ * GW_SPAN_STEP_HORIZON the two launches of gw_step_horizon (preview_rec_kernel, step_horizon_kernel),
+ * GW_SPAN_STEP_PLAN the two launches of gw_step_plan (preview_rec_kernel, step_plan_kernel).
  * enable > 1 also makes sure `enable` timing events exist now (creating them inside a profiled
  * step would put their host cost between its launches).  gw_profile_read synchronises on those
  * events, returns the summed elapsed milliseconds of the first three kinds and the number of
@@ -181,7 +182,8 @@ enum {
     GW_SPAN_STEP_PREVIEW = 14 /* the two launches of one gw_step_preview (preview_rec_kernel, step_preview_kernel) */,
     GW_SPAN_CRASH_SHIELD = 15 /* the two launches of one gw_crash_shield_joint (preview_rec_kernel, crash_shield_joint_kernel) */,
     GW_SPAN_STEP_LOOKAHEAD = 16 /* the two launches of one gw_step_lookahead (preview_rec_kernel, step_lookahead_kernel) */,
-    GW_SPAN_STEP_HORIZON = 17 /* the two launches of one gw_step_horizon (preview_rec_kernel, step_horizon_kernel) */
+    GW_SPAN_STEP_HORIZON = 17 /* the two launches of one gw_step_horizon (preview_rec_kernel, step_horizon_kernel) */,
+    GW_SPAN_STEP_PLAN = 18 /* the two launches of one gw_step_plan (preview_rec_kernel, step_plan_kernel) */
 };
 gw_status gw_profile(void *env, int enable);
 gw_status gw_profile_read(void *env, double out_ms[3], int64_t *n_steps);
@@ -610,6 +612,49 @@ gw_status gw_step_lookahead(void *env, const int32_t *rl_actions, const int32_t 
 gw_status gw_step_horizon(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask, int horizon,
                           uint8_t *depth, uint16_t *ends, uint16_t *crash9, uint16_t *viable9, uint16_t *horizon_mask,
                           int32_t *actions, int32_t *mdr, void *stream);
+
+/* The reward horizon: for each RL agent k and first action a, how many of the next H steps k can survive AND the
+ * largest env reward those steps can pay it, without moving the world.  gw_step_horizon tells which first actions
+ * keep k alive; it removes the apples after step 1, so it cannot tell which of them is worth taking.  Arguments,
+ * preconditions, status codes and capture rules are gw_step_horizon's; `horizon` is H, 2 <= H <= GW_HORIZON_MAX.
+ * Step 1 is exactly gw_step_preview's task, and its reward is reward_alt[e][k][a], bit for bit, times 10.
+ * Steps 2..H run the real world update WITH apples (eaters 0..K-1) while the episode goes on: every other RL agent
+ *   plays 0 (stay; the one assumption, exact for K = 1), the scripted agents play their recomputed Philox draws (a
+ *   caller's `scripted` override holds for step 1 only), and agent k plays an action the action mask of the cell it
+ *   stands in allows.  Each step carries the apples, the term / trunc flags and k's prev_dist that the steps before
+ *   it left; its `done` and its reward for k are the step's own rules on that state, so eating the env's last apple
+ *   ends the episode, and so do the step cap and another RL agent's crash.
+ * depth [E][K][9] u8 in 0..H: gw_step_horizon's definition on this world: the largest d for which some continuation
+ *   keeps k from crashing in the steps 1..d; an episode end without k's own crash, the horizon, or a cell whose
+ *   action mask is empty counts as H.  (It is never below gw_step_horizon's depth: the apples add episode ends.)
+ * ret [E][K][9] i16, in tenths of a reward unit: the largest sum of env rewards the steps of a continuation pay
+ *   agent k, over the continuations that reach depth[e][k][a].  Continuations are ordered lexicographically by
+ *   (depth, return): survival first, return second.  A continuation that ends below H includes its one crash (-100);
+ *   a continuation stops at an episode end, at the horizon, and in a cell that allows nothing.
+ * path [E][K][9][GW_HORIZON_MAX - 1] u8: the actions after a of the continuation that attains (depth, ret); ties go
+ *   to the lowest action at every level.  The crash step, the step that ends the episode and step H are the path's
+ *   last entry; entries past the end are 0xFF (all of them where a itself crashes k or ends the episode).
+ * ends, crash9 [E][K] u16: gw_step_horizon's, bit for bit.
+ * plan_mask [E][K] u16: with m = mask[e][k] (mask [E][K] 9-bit action masks; NULL: 0x1FF), the actions of m whose
+ *   (depth, ret) is the lexicographic maximum over m; m == 0 gives 0.  Its actions all have the maximal depth over
+ *   m, so it is a subset of what gw_step_horizon's rule gives on this depth table.  Passed to gw_fear_shield in the
+ *   action mask's place it makes the shield pick among the actions that keep the agent alive longest and, of
+ *   those, collect the most reward.  The rules are csrc/step_plan.h's.
+ * Each of depth, ret, path, ends, crash9 and plan_mask may be NULL; actions / mdr as in gw_step_horizon.
+ * How it is computed: while k has not crashed the world differs between k's choices in two things only, k's cell
+ * and whether k's apple is still there (motion and crashes do not depend on apples; the other agents' apples
+ * belong to the level's one background; k's prev_dist is a function of its cell and its apple bit), so a node is
+ * still a cell.  Every (node, allowed action) is one world update with k's apple present; the backward pass keeps
+ * two values per node: the depth without k's apple (gw_step_horizon's recursion; the return from there is 0 if it
+ * reaches H, else -100) and the best (depth, return) with it.
+ * GW_ERR_ARG also on a ret array that is not 2-byte aligned.
+ * Cost: two launches on `stream` (preview_rec_kernel, then step_plan_kernel: one wave per env, the RL agents in
+ * turn), one GW_SPAN_STEP_PLAN span while profiling.  gw_count_sims counts as gw_step_horizon does: per env 9 K for
+ * step 1 plus one world update per reached level, distinct cell k can stand in there (with or without its apple)
+ * and action that cell's mask allows. */
+gw_status gw_step_plan(void *env, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask, int horizon,
+                       uint8_t *depth, int16_t *ret, uint8_t *path, uint16_t *ends, uint16_t *crash9, uint16_t *plan_mask,
+                       int32_t *actions, int32_t *mdr, void *stream);
 
 /* The coordinated crash-aware shield: gw_step_preview's safe masks inside gw_fear_shield_joint's sweeps, in one call.
  * The crash-aware shield built from gw_step_preview and gw_fear_shield is unilateral: an agent moved to a safe action

@@ -572,6 +572,25 @@ struct StepHorizonArgs {
 hipError_t launch_step_horizon(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
                                const StepHorizonArgs &a);
 
+// gw_step_plan's arguments beside the env's (include/gridenv.h): mask [E][K] or null, horizon in 2..GW_HORIZON_MAX,
+// depth [E][K][9] / ret [E][K][9] / path [E][K][9][GW_HORIZON_MAX - 1] / ends [E][K] / crash9 [E][K] /
+// plan_mask [E][K] or null
+struct StepPlanArgs {
+    const uint16_t *mask;
+    int horizon;
+    uint8_t *depth;
+    int16_t *ret;
+    uint8_t *path;
+    uint16_t *ends;
+    uint16_t *crash9;
+    uint16_t *plan_mask;
+};
+
+// step_plan_kernel<N> (step_plan.hip, gw_step_plan) over p's env range on s, through gwprof::launch, from the
+// record in p.fwork
+hipError_t launch_step_plan(int N, dim3 grid, dim3 block, size_t dyn, hipStream_t s, const Params &p,
+                            const StepPlanArgs &a);
+
 // The arguments of the two joint shields beside the env's (include/gridenv.h; the kernels' one body:
 // shield_joint_core.h): mask [E][K] or null, probs [K][E][9] or null, agents / sweeps already checked,
 // actions_out [E][K], flags [E][K] / table [E][K][9] / joint [E][N] or null.  gw_crash_shield_joint alone reads

@@ -3026,6 +3026,26 @@ gw_status gw_step_horizon(void *handle, const int32_t *rl_actions, const int32_t
                         });
 }
 
+gw_status gw_step_plan(void *handle, const int32_t *rl_actions, const int32_t *scripted, const uint16_t *mask, int horizon,
+                       uint8_t *depth, int16_t *ret, uint8_t *path, uint16_t *ends, uint16_t *crash9, uint16_t *plan_mask,
+                       int32_t *actions, int32_t *mdr, void *stream) {
+    Env *env = static_cast<Env *>(handle);
+    if (!env) return fail(GW_ERR_ARG, "gw_step_plan: null env");
+    if (horizon < 2 || horizon > GW_HORIZON_MAX) return fail(GW_ERR_ARG, "gw_step_plan: need 2 <= horizon <= GW_HORIZON_MAX");
+    for (const void *q : {(const void *)mask, (const void *)ret, (const void *)ends, (const void *)crash9,
+                          (const void *)plan_mask})
+        if (reinterpret_cast<uintptr_t>(q) & 1u) return fail(GW_ERR_ARG, "gw_step_plan: a 16-bit array not 2-byte aligned");
+    // the kernel keeps a cell and an action in one u16 (cell | action << 12)
+    if (env->HW > 4096) return fail(GW_ERR_ARG, "gw_step_plan: needs H*W <= 4096");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const gw::StepPlanArgs a{mask, horizon, depth, ret, path, ends, crash9, plan_mask};
+    // every level's world updates on the record (step_plan.hip); gw_step_preview's record buffer
+    return preview_call(env, "gw_step_plan", &env->step_preview_rec, GW_SPAN_STEP_PLAN, rl_actions, scripted,
+                        actions, mdr, s, [&](dim3 grid, dim3 block, size_t dyn, const gw::Params &q) {
+                            return gw::launch_step_plan(env->N, grid, block, dyn, s, q, a);
+                        });
+}
+
 gw_status gw_fear_preview(void *handle, const int32_t *rl_actions, const int32_t *scripted, double *fear_alt,
                           int32_t *actions, int32_t *mdr, void *stream) {
     Env *env = static_cast<Env *>(handle);

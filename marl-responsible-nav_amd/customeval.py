@@ -72,7 +72,20 @@ def main(argv=None):
                          "after the first step); implies --shield-crash and also prints how many proposals were "
                          "doomed, how many of them were replaced and how many agent-steps had no viable action.  "
                          "Unilateral: not with --shield-mode joint or joint_crash, nor with --shield-lookahead")
+    ap.add_argument("--shield-plan", type=int, default=None, metavar="H",
+                    help="plan shield (H in 2..4; default off): the horizon shield on the world with its apples; it "
+                         "keeps an agent to the actions that keep it alive longest and, of those, collect the most "
+                         "reward over H steps; implies --shield-crash and also prints how many proposals were not "
+                         "in the plan mask and how many of them were replaced.  Unilateral: not with --shield-mode "
+                         "joint or joint_crash, nor with --shield-lookahead or --shield-horizon")
     args = ap.parse_args(argv)
+    if args.shield_plan is not None:
+        if not 2 <= args.shield_plan <= 4:
+            ap.error("--shield-plan: 2, 3 or 4")
+        if args.shield_mode != "unilateral":
+            ap.error("--shield-plan is unilateral: not with --shield-mode joint or joint_crash")
+        if args.shield_lookahead or args.shield_horizon is not None:
+            ap.error("--shield-plan looks ahead itself: not with --shield-lookahead or --shield-horizon")
     if args.shield_horizon is not None:
         if not 2 <= args.shield_horizon <= 4:
             ap.error("--shield-horizon: 2, 3 or 4")
@@ -107,7 +120,8 @@ def main(argv=None):
                  seed=args.seed, variant=variant, feal=args.feal, resp_full=args.resp_full, shield=args.shield,
                  shield_mode=args.shield_mode, shield_sweeps=args.shield_sweeps, resp_map=resp_map,
                  resp_footprint=args.resp_footprint, shield_crash=args.shield_crash,
-                 shield_lookahead=args.shield_lookahead, shield_horizon=args.shield_horizon)
+                 shield_lookahead=args.shield_lookahead, shield_horizon=args.shield_horizon,
+                 shield_plan=args.shield_plan)
     n = args.episodes
     print(f"Total destination reached: {r['apples_caught']} across {n} episodes")
     print(f"Total crashes: {r['crashes']} across {n} episodes")
@@ -126,7 +140,7 @@ def main(argv=None):
               f"proposals would have crashed the agent, {r['shield_crash_final'].tolist()} applied actions did, "
               f"{r['shield_unavoidable'].tolist()} visits had no crash-free action, agent-steps per RL agent; "
               f"{r['shield_unconverged']} env-steps unconverged")
-    elif args.shield_crash or args.shield_lookahead or args.shield_horizon is not None:
+    elif args.shield_crash or args.shield_lookahead or args.shield_horizon is not None or args.shield_plan is not None:
         print(f"Crash shield: {r['shield_crash_proposed'].tolist()} proposals would have crashed the agent, "
               f"{r['shield_crash_replaced'].tolist()} of them replaced, agent-steps per RL agent")
     if args.shield_lookahead:
@@ -136,6 +150,9 @@ def main(argv=None):
         print(f"Horizon shield (H = {args.shield_horizon}): {r['shield_doomed_proposed'].tolist()} proposals were "
               f"doomed, {r['shield_doomed_replaced'].tolist()} of them replaced, "
               f"{r['shield_no_viable'].tolist()} had no viable action, agent-steps per RL agent")
+    if args.shield_plan is not None:
+        print(f"Plan shield (H = {args.shield_plan}): {r['shield_plan_proposed_off'].tolist()} proposals were not in "
+              f"the plan mask, {r['shield_plan_replaced'].tolist()} of them replaced, agent-steps per RL agent")
     if args.feal:
         print("Mean FeAL per agent: " + " ".join(f"{v:.6f}" for v in r["feal"].tolist()))
     if args.resp_full:

@@ -32,7 +32,7 @@ HIP_SOURCES = [os.path.join(CSRC, "gridenv.hip"), os.path.join(CSRC, "learner_op
                os.path.join(CSRC, "fear_cf.hip"), os.path.join(CSRC, "fear_matrix.hip"),
                os.path.join(CSRC, "resp_footprint.hip"), os.path.join(CSRC, "step_preview.hip"),
                os.path.join(CSRC, "crash_shield_joint.hip"), os.path.join(CSRC, "step_lookahead.hip"),
-               os.path.join(CSRC, "step_horizon.hip")]
+               os.path.join(CSRC, "step_horizon.hip"), os.path.join(CSRC, "step_plan.hip")]
 HEADERS = [os.path.join(INCLUDE, "gridenv.h"), os.path.join(INCLUDE, "learner_ops.h"),
            os.path.join(INCLUDE, "actor_ops.h"), os.path.join(INCLUDE, "rollout_ops.h")]
 SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.join(CSRC, "window_rows.h"), os.path.join(CSRC, "prof.h"),
@@ -47,7 +47,8 @@ SOURCES = HIP_SOURCES + HEADERS + [os.path.join(CSRC, "patch_ops.h"), os.path.jo
                                    os.path.join(CSRC, "resp_footprint.h"), os.path.join(CSRC, "step_preview.h"),
                                    os.path.join(CSRC, "crash_shield.h"), os.path.join(CSRC, "shield_joint_core.h"),
                                    os.path.join(CSRC, "step_lookahead.h"), os.path.join(CSRC, "preview_done.h"),
-                                   os.path.join(CSRC, "step_horizon.h")]
+                                   os.path.join(CSRC, "step_horizon.h"), os.path.join(CSRC, "step_plan.h"),
+                                   os.path.join(CSRC, "preview_reward.h"), os.path.join(CSRC, "horizon_window.h")]
 OBJ_DIR = os.path.join(CSRC, "build_measure" if MEASURE else "build")
 ARCH = os.environ.get("MARLNAV_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -211,7 +212,7 @@ EXPORTS = ["gw_create", "gw_reset", "gw_step", "gw_state_view", "gw_copy_state",
            "gw_set_obs_delta", "gw_obs_dest_forget", "gw_obs_delta_counts", "gw_set_obs_ride", "gw_obs_ride_count",
            "gw_set_feal", "gw_feal_accum", "gw_set_fear_full", "gw_fear_preview", "gw_fear_shield",
            "gw_fear_shield_joint", "gw_resp_map_accum", "gw_resp_footprint_accum", "gw_step_preview",
-           "gw_crash_shield_joint", "gw_step_lookahead", "gw_step_horizon"]
+           "gw_crash_shield_joint", "gw_step_lookahead", "gw_step_horizon", "gw_step_plan"]
 
 
 class GwObsSource(C.Structure):
@@ -381,6 +382,8 @@ def _declare(L):
     L.gw_step_lookahead.restype = C.c_int
     L.gw_step_horizon.argtypes = [p] * 4 + [C.c_int] + [p] * 8
     L.gw_step_horizon.restype = C.c_int
+    L.gw_step_plan.argtypes = [p] * 4 + [C.c_int] + [p] * 9
+    L.gw_step_plan.restype = C.c_int
     L.gw_crash_shield_joint.argtypes = [p, p, p, p, p, C.c_int32, C.c_double, C.c_uint32, C.c_int32] + [p] * 8
     L.gw_crash_shield_joint.restype = C.c_int
     L.gw_resp_map_accum.argtypes = [p, p, p, p, p, C.c_int32, C.c_int32, C.c_int32, p]

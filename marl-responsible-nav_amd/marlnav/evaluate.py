@@ -38,7 +38,8 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
              feal: bool = False, resp_full: bool = False, shield: float | None = None,
              shield_mode: str = "unilateral", shield_sweeps: int = 2, resp_map: bool = False,
              resp_footprint: int | None = None, shield_crash: bool = False,
-             shield_lookahead: bool = False, shield_horizon: int | None = None) -> dict:
+             shield_lookahead: bool = False, shield_horizon: int | None = None,
+             shield_plan: int | None = None) -> dict:
     """The responsibility folds (marlnav/resp_folds.py: each class says what it sums), over the episodes still
     running; all but ``resp_matrix`` raise ValueError without ``fear=True``.  f64 / int64 CPU tensors:
       resp_matrix: "resp" [K, N], the summed rows divided by "steps".
@@ -70,19 +71,30 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         picks among the masked actions that keep the agent alive longest over H steps; ``shield_crash`` is implied;
         also "shield_doomed_proposed" [K] (the proposal's depth was below H while a viable action existed),
         "shield_doomed_replaced" [K] and "shield_no_viable" [K].  Unilateral: ValueError with a joint mode or
-        with ``shield_lookahead=True``."""
-    check_shield_args(shield_mode, shield_crash, "evaluate", shield_lookahead, shield_horizon)
+        with ``shield_lookahead=True``.
+      shield_plan: the plan shield (``VecGridEnv.step_plan``, an int H in 2..4): the crash-aware shield that picks
+        among the masked actions that keep the agent alive longest over H steps and, of those, collect the most
+        env reward ("plan_mask"); ``shield_crash`` is implied; also "shield_plan_proposed_off" [K] (the proposal
+        was not in the plan mask) and "shield_plan_replaced" [K].  Unilateral: ValueError with a joint mode, with
+        ``shield_lookahead=True`` or with ``shield_horizon``.  ``actors=None`` with ``shield_plan=H`` is the
+        policy-free planner, a model-predictive baseline: every RL agent proposes 0 and takes the lowest action of
+        its plan mask, re-planned every step (``actors=None`` without ``shield_plan`` is a ValueError)."""
+    check_shield_args(shield_mode, shield_crash, "evaluate", shield_lookahead, shield_horizon, shield_plan)
+    if actors is None and shield_plan is None:
+        raise ValueError("evaluate(actors=None) needs shield_plan=H: the policy-free planner")
     for kw, on in (("fear_regret=True", fear_regret), ("feal=True", feal), ("resp_full=True", resp_full),
                    ("resp_map=True", resp_map), ("resp_footprint=R", resp_footprint is not None)):
         if on and not fear:
             raise ValueError(f"evaluate({kw}) needs fear=True")
     footprint = resp_footprint is not None
     sc = builtin(scenario) if isinstance(scenario, str) else scenario
+    if actors is None:
+        fused = False
     if fused is None:
         fused = actors.fusable(SimpleNamespace(K=sc.K, H=sc.H, W=sc.W))
     # the fused actor reads the obs descriptors: no dense obs is written at all
     env = VecGridEnv(sc, num_envs=episodes, fear=fear, max_steps=max_steps, auto_reset=False, seed=seed,
-                     obs=not fused, variant=variant, fear_rows=resp_matrix, fear_alt=fear_regret, feal=feal,
+                     obs=not fused and actors is not None, variant=variant, fear_rows=resp_matrix, fear_alt=fear_regret, feal=feal,
                      fear_full=resp_full or resp_map or footprint, debug=footprint)
     try:
         obs, mask = env.reset()
@@ -94,18 +106,22 @@ def evaluate(actors: MultiAgentActors, scenario="level3", episodes: int = 100, m
         folds, cells = build_folds(env, "evaluate", resp_matrix, fear_regret, feal, resp_full, resp_map, resp_footprint)
         guard = None
         if (shield is not None or shield_crash or shield_lookahead or shield_horizon is not None
-                or shield_mode == "joint_crash"):
+                or shield_plan is not None or shield_mode == "joint_crash"):
             guard = Shield(env, shield, shield_mode, shield_sweeps, shield_crash, count_crash=True, who="evaluate",
-                           lookahead=shield_lookahead, horizon=shield_horizon)
+                           lookahead=shield_lookahead, horizon=shield_horizon, plan=shield_plan)
+        stay = torch.zeros((episodes, env.K), dtype=torch.int32, device=dev) if actors is None else None
         recorded = []
         alive = torch.zeros(max_steps, dtype=torch.bool, device=dev) if record_actions else None
         for i in range(max_steps):
-            if fused:  # one kernel over the obs descriptors (include/actor_ops.h)
+            if actors is None:  # the policy-free planner: the shield alone decides
+                actions, probs = stay, None
+            elif fused:  # one kernel over the obs descriptors (include/actor_ops.h)
                 actions, probs = actors.act_env(env, env.out["mask"], training=False)
             else:
                 actions, probs = actors.act(env.out["obs"], env.out["mask"], training=False)
             if guard is not None:  # actor -> preview(s) -> shield -> step
-                actions = guard.apply(env, actions, probs.contiguous(), env.out["mask"], active=active)
+                actions = guard.apply(env, actions, None if probs is None else probs.contiguous(), env.out["mask"],
+                                      active=active)
             if record_actions:
                 recorded.append(actions.clone())
             if cells is not None:  # the step's pre-move cells

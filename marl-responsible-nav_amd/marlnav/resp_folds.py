@@ -219,8 +219,17 @@ def fold_results(folds, widths, flat, all_reduce=None) -> dict:
 
 
 def check_shield_args(shield_mode: str, shield_crash: bool, who: str = "Rollout", shield_lookahead: bool = False,
-                      shield_horizon: int | None = None):
+                      shield_horizon: int | None = None, shield_plan: int | None = None):
     """The shield keywords' checks (no device needed)."""
+    if shield_plan is not None:
+        if isinstance(shield_plan, bool) or not 2 <= int(shield_plan) <= GW_HORIZON_MAX:
+            raise ValueError(f"{who}(shield_plan=...): None or an int in 2..{GW_HORIZON_MAX}")
+        if shield_lookahead or shield_horizon is not None:
+            raise ValueError(f"{who}(shield_plan={shield_plan}) with shield_lookahead or shield_horizon: the plan shield "
+                             "looks ahead itself; pick one")
+        if shield_mode in ("joint", "joint_crash"):
+            raise ValueError(f'{who}(shield_plan={shield_plan}) with shield_mode="{shield_mode}": the plan shield is '
+                             "unilateral")
     if shield_horizon is not None:
         if isinstance(shield_horizon, bool) or not 2 <= int(shield_horizon) <= GW_HORIZON_MAX:
             raise ValueError(f"{who}(shield_horizon=...): None or an int in 2..{GW_HORIZON_MAX}")
@@ -267,6 +276,12 @@ class Shield:
         ``env.step_horizon(horizon=H)`` in ``step_preview``'s place and its "horizon_mask" (the masked actions that
         keep the agent alive longest over H steps, the other RL agents staying after the first) in the safe
         mask's.  ``depth`` / ``viable9`` hold the last step's [E, K, 9] depths and [E, K] viable sets.
+      plan (``plan=H``, unilateral only, not with lookahead or horizon; ``crash`` is implied): the crash-aware
+        pipeline with ``env.step_plan(horizon=H)`` in ``step_preview``'s place and its "plan_mask" (of the masked
+        actions that keep the agent alive longest over H steps, the ones whose best continuation collects the most
+        env reward) in the safe mask's.  ``depth`` / ``ret`` / ``plan_mask`` hold the last step's tables.  With
+        ``probs=None`` or one-hot probabilities ``env.fear_shield`` picks the lowest action of the plan mask:
+        the policy-free planner.
     ``flags`` holds the last step's [E, K] uint8 flags.  ``totals()``: "shield_replaced" [K] and "shield_stuck"
     [K] (int64 CPU tensors: the agent-steps whose action was replaced, flag bit 0 / that had no allowed action,
     bit 1); joint: also "shield_over" [K] (the applied action's FeAR exceeds tau, bit 2) and
@@ -278,14 +293,17 @@ class Shield:
     "shield_trap_proposed" [K] and "shield_trap_replaced" [K] (the agent-steps whose proposed action was a trap
     action / of those, the ones replaced); horizon: also "shield_doomed_proposed" [K] (the proposal's depth was
     below H while some action of the mask was viable), "shield_doomed_replaced" [K] (of those, the ones replaced)
-    and "shield_no_viable" [K] (no action of the mask was viable)."""
+    and "shield_no_viable" [K] (no action of the mask was viable); plan: also "shield_plan_proposed_off" [K] (the
+    proposal was not in the plan mask) and "shield_plan_replaced" [K] (of those, the ones replaced)."""
 
     def __init__(self, env, tau: float | None, mode: str = "unilateral", sweeps: int = 2, crash: bool = False,
-                 count_crash: bool = False, who: str = "Rollout", lookahead: bool = False, horizon: int | None = None):
-        check_shield_args(mode, crash, who, lookahead, horizon)
+                 count_crash: bool = False, who: str = "Rollout", lookahead: bool = False, horizon: int | None = None,
+                 plan: int | None = None):
+        check_shield_args(mode, crash, who, lookahead, horizon, plan)
         self.lookahead = bool(lookahead)
         self.horizon = None if horizon is None else int(horizon)
-        crash = bool(crash) or self.lookahead or self.horizon is not None
+        self.plan = None if plan is None else int(plan)
+        crash = bool(crash) or self.lookahead or self.horizon is not None or self.plan is not None
         E, K, dev = env.E, env.K, env.device
         self.tau = None if tau is None else float(tau)
         self.joint_crash = mode == "joint_crash"
@@ -301,6 +319,9 @@ class Shield:
         # doomed proposals, of those replaced, agent-steps without a viable action
         self.doomed_cnt = torch.zeros((3, K), dtype=torch.int64, device=dev) if self.horizon is not None else None
         self.depth = self.viable9 = None
+        # proposals outside the plan mask, of those replaced
+        self.plan_cnt = torch.zeros((2, K), dtype=torch.int64, device=dev) if self.plan is not None else None
+        self.ret = self.plan_mask = None
         if self.joint_crash:  # proposal crashes, final crashes, unavoidable
             self.crash_cnt = torch.zeros((3, K), dtype=torch.int64, device=dev)
             self._outcome_prop = torch.empty(E, dtype=torch.int16, device=dev)
@@ -349,7 +370,10 @@ class Shield:
                 env.fear_preview(actions, out=self._table)
         if self.crash:  # the shield picks among the actions under which the agent itself does not crash
             m_in = mask
-            if self.horizon is not None:  # ... and that keeps the agent alive longest
+            if self.plan is not None:  # ... that keeps the agent alive longest and collects the most reward
+                sp = env.step_plan(actions, None, mask=mask, horizon=self.plan)
+                self.depth, self.ret, self.plan_mask = sp["depth"], sp["ret"], sp["plan_mask"]
+            elif self.horizon is not None:  # ... and that keeps the agent alive longest
                 sp = env.step_horizon(actions, None, mask=mask, horizon=self.horizon)
                 self.depth, self.viable9 = sp["depth"], sp["viable9"]
             elif self.lookahead:  # ... and that is no trap action
@@ -358,7 +382,8 @@ class Shield:
                 sp = env.step_preview(actions, None, mask=mask, reward=False)
             if actions is None:
                 actions = sp["actions"][:, :env.K].contiguous()
-            which = "horizon_mask" if self.horizon is not None else "ahead_mask" if self.lookahead else "safe_mask"
+            which = ("plan_mask" if self.plan is not None else "horizon_mask" if self.horizon is not None else
+                     "ahead_mask" if self.lookahead else "safe_mask")
             mask, self.crash9 = sp[which], sp["crash9"]
             self.trap9 = sp.get("trap9")
         out, flags = env.fear_shield(self._table, actions, mask=mask, probs=probs,
@@ -378,6 +403,10 @@ class Shield:
             count(self.doomed_cnt[0], doomed)
             count(self.doomed_cnt[1], doomed * (out != actions).to(torch.int64))
             count(self.doomed_cnt[2], 1 - some)
+        if self.plan_cnt is not None:
+            off = 1 - ((self.plan_mask.to(torch.int64) >> actions.to(torch.int64)) & 1)
+            count(self.plan_cnt[0], off)
+            count(self.plan_cnt[1], off * (out != actions).to(torch.int64))
         count(self.cnt[0], flags & 1)
         count(self.cnt[1], flags >> 1)
         return out
@@ -397,6 +426,9 @@ class Shield:
         if self.doomed_cnt is not None:
             dc = _summed(self.doomed_cnt, all_reduce)
             out["shield_doomed_proposed"], out["shield_doomed_replaced"], out["shield_no_viable"] = dc[0], dc[1], dc[2]
+        if self.plan_cnt is not None:
+            pc = _summed(self.plan_cnt, all_reduce)
+            out["shield_plan_proposed_off"], out["shield_plan_replaced"] = pc[0], pc[1]
         cnt = _summed(self.cnt, all_reduce)
         out["shield_replaced"], out["shield_stuck"] = cnt[0], cnt[1]
         if self.joint:

@@ -215,7 +215,7 @@ class Rollout:
                  fear_regret: bool = False, feal: bool = False, resp_full: bool = False,
                  shield: float | None = None, shield_mode: str = "unilateral", shield_sweeps: int = 2,
                  resp_map: bool = False, resp_footprint: int | None = None, shield_crash: bool = False,
-                 shield_lookahead: bool = False, shield_horizon: int | None = None):
+                 shield_lookahead: bool = False, shield_horizon: int | None = None, shield_plan: int | None = None):
         """fused: get_action as the one-kernel gw_actor_act over the env's obs descriptors
         (default when the actors are the f32 128-128 MLP), else the PyTorch forward over the
         dense obs with torch's Gumbel noise.
@@ -278,6 +278,12 @@ class Rollout:
             implied; ``shield_depth`` / ``shield_viable9`` hold the last step's [E, K, 9] depths and [E, K] viable
             sets; also "shield_doomed_proposed" [K], "shield_doomed_replaced" [K], "shield_no_viable" [K].
             Unilateral: ValueError with a joint mode or with ``shield_lookahead=True``.
+          shield_plan: the plan shield (``env.step_plan``, an int H in 2..4): the crash-aware shield that picks
+            among the masked actions that keep the agent alive longest over H steps and, of those, collect the
+            most env reward; ``shield_crash`` is implied; ``shield_depth`` / ``shield_ret`` / ``shield_plan_mask``
+            hold the last step's [E, K, 9] depths and returns (int16 tenths) and [E, K] plan masks; also
+            "shield_plan_proposed_off" [K], "shield_plan_replaced" [K].  Unilateral: ValueError with a joint
+            mode, with ``shield_lookahead=True`` or with ``shield_horizon``.
         Eager only: ``capture`` raises ValueError."""
         self.env = env
         self.actors = actors
@@ -356,23 +362,25 @@ class Rollout:
         self._pending = None  # (stats, tick) of a step whose FeAR may still be in flight
         self._folds, self._cells = build_folds(env, "Rollout", resp_matrix, fear_regret, feal, resp_full, resp_map,
                                                resp_footprint)
-        self.check_shield_args(shield_mode, shield_crash, "Rollout", shield_lookahead, shield_horizon)
+        self.check_shield_args(shield_mode, shield_crash, "Rollout", shield_lookahead, shield_horizon, shield_plan)
         self.shield = None if shield is None else float(shield)
         self.shield_lookahead = bool(shield_lookahead)
         self.shield_horizon = None if shield_horizon is None else int(shield_horizon)
         self.shield_mode, self.shield_sweeps = shield_mode, int(shield_sweeps)
-        self.shield_crash = bool(shield_crash) or self.shield_lookahead or self.shield_horizon is not None
+        self.shield_plan = None if shield_plan is None else int(shield_plan)
+        self.shield_crash = (bool(shield_crash) or self.shield_lookahead or self.shield_horizon is not None
+                             or self.shield_plan is not None)
         self._shield = None
         if self.shield is not None or self.shield_crash or shield_mode == "joint_crash":
             self._shield = Shield(env, self.shield, shield_mode, shield_sweeps, self.shield_crash,
-                                  lookahead=self.shield_lookahead, horizon=self.shield_horizon)
+                                  lookahead=self.shield_lookahead, horizon=self.shield_horizon, plan=self.shield_plan)
 
     check_shield_args = staticmethod(check_shield_args)
 
     # the shield's last-step tensors (None without a shield / outside the mode that fills them)
-    shield_flags, shield_table, shield_crash9, shield_trap9, shield_depth, shield_viable9 = (
+    shield_flags, shield_table, shield_crash9, shield_trap9, shield_depth, shield_viable9, shield_ret, shield_plan_mask = (
         property(lambda self, n=n: getattr(self._shield, n, None))
-        for n in ("flags", "table", "crash9", "trap9", "depth", "viable9"))
+        for n in ("flags", "table", "crash9", "trap9", "depth", "viable9", "ret", "plan_mask"))
 
     def group_rank(self) -> int:
         return dist.get_rank(self.group) if self.distributed else 0

@@ -908,6 +908,51 @@ class VecGridEnv:
                                                 _ptr(buf["mdr"]), self._stream()), "gw_step_horizon")
         return dict(buf)
 
+    def step_plan(self, rl_actions: torch.Tensor | None = None, scripted: torch.Tensor | None = None,
+                  mask: torch.Tensor | None = None, horizon: int = 3) -> dict:
+        """The reward horizon (gw_step_plan): for each RL agent and first action, how many of the next ``horizon``
+        steps (2..4) the agent can survive and the most env reward those steps can pay it, without moving the
+        world.  ``step_horizon`` on the world with its real apples: after the first step the other RL agents stay
+        (action 0), the scripted agents play their draws, k plays what its cell's action mask allows, and every step
+        is the real world update with the step's own reward and ``done`` rules (eating the last apple ends the
+        episode).  -> a dict of tensors, allocated once and reused by every call:
+          "depth" [E, K, 9] uint8 in 0..horizon: ``step_horizon``'s definition on that world;
+          "ret" [E, K, 9] int16, in tenths of a reward unit: the largest sum of env rewards over the continuations
+            that reach "depth" (survival first, return second); a continuation below ``horizon`` includes its one
+            crash (-100);
+          "path" [E, K, 9, 3] uint8: the actions after a of the continuation that attains ("depth", "ret"), ties to
+            the lowest action; the crash step or the step that ends the episode is its last entry, 0xFF after it;
+          "ends" / "crash9" [E, K] int16: ``step_horizon``'s, bit for bit;
+          "plan_mask" [E, K] int16: the actions of ``mask`` (None: all nine) whose ("depth", "ret") is the
+            lexicographic maximum over the mask;
+          "actions" [E, N] / "mdr" [E, N] int32: the joint action that step will apply and the cells' MdR.
+        None arguments mean what they mean for ``step``; a ``scripted`` override holds for the first step only.
+        Works with ``fear=False``.  Changes no env state."""
+        E, K, N = self.E, self.K, self.N
+        if isinstance(horizon, bool) or not 2 <= int(horizon) <= 4:
+            raise ValueError("step_plan(horizon=...): an int in 2..4 (GW_HORIZON_MAX)")
+        self._check_counts("step_plan", rl_actions=(rl_actions, E * K), scripted=(scripted, E * (N - K)))
+        self._check_bufs("step_plan", dict(mask=mask), dict(mask=(torch.int16, E * K)), self.device,
+                         note=" (the 9-bit action masks, as StepResult.mask)")
+        rl = self._as_i32(rl_actions, (E, K))
+        sa = self._as_i32(scripted, (E, N - K))
+        buf = getattr(self, "_step_plan_out", None)
+        if buf is None:
+            i16 = dict(dtype=torch.int16, device=self.device)
+            i32 = dict(dtype=torch.int32, device=self.device)
+            u8 = dict(dtype=torch.uint8, device=self.device)
+            buf = dict(depth=torch.zeros((E, K, 9), **u8), ret=torch.zeros((E, K, 9), **i16),
+                       path=torch.zeros((E, K, 9, 3), **u8), ends=torch.zeros((E, K), **i16),
+                       crash9=torch.zeros((E, K), **i16), plan_mask=torch.zeros((E, K), **i16),
+                       actions=torch.zeros((E, N), **i32), mdr=torch.zeros((E, N), **i32))
+            self._step_plan_out = buf
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gw_step_plan(self.handle, _ptr(rl), _ptr(sa), _ptr(mask), int(horizon),
+                                             _ptr(buf["depth"]), _ptr(buf["ret"]), _ptr(buf["path"]), _ptr(buf["ends"]),
+                                             _ptr(buf["crash9"]), _ptr(buf["plan_mask"]), _ptr(buf["actions"]),
+                                             _ptr(buf["mdr"]), self._stream()), "gw_step_plan")
+        return dict(buf)
+
     def obs_patch(self, size: int, final: bool = False, out: torch.Tensor | None = None,
                   final_out: torch.Tensor | None = None):
         """Egocentric local observations (gw_obs_patch): [K, E, size, size] float32, agent k's obs
